@@ -15,12 +15,57 @@ Metric: es_rollouts_per_sec — completed env episodes per second, whole
 job (a rollout = one episode of one env instance: pop_total x 64 envs
 per iteration).  Synthetic data, random-init weights (no datasets in
 this environment); weak scaling (per-GPU population fixed).
+
+A plain run sets up, warms up, times --steps iterations and prints one
+JSON line; it measures nothing else.  --dump-outputs DIR additionally
+writes what the last timed step produced (see dump_outputs).  --full is
+the switch for measurements beyond the headline figure; the benchmark
+has none today, so it currently changes nothing.
 """
 
 import argparse
 import json
 import os
 import time
+
+
+# Outputs are tiny for both configs (MLP: 3 x 4610 floats; conv: 3 x
+# ~1.7M); the cap only guards a future, larger policy.
+DUMP_BYTE_CAP = 64 << 20
+STAT_KEYS = ("fitness_mean", "fitness_max", "grad_norm", "rollouts",
+             "env_steps")
+
+
+def stats_array(stats):
+    """The stats dict step() returns, as a float64 vector (STAT_KEYS
+    order)."""
+    import numpy as np
+
+    return np.array([float(stats[k]) for k in STAT_KEYS], dtype=np.float64)
+
+
+def dump_outputs(directory, arrays):
+    """Write {name: ndarray} as DIR/<name>.npy (float32/float64).  If the
+    set exceeds DUMP_BYTE_CAP every array is cut to a fixed seeded sample
+    of equal share, so two builds still dump the same elements."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    arrays = {
+        name: np.ascontiguousarray(
+            a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        for name, a in arrays.items()
+    }
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BYTE_CAP:
+        share = DUMP_BYTE_CAP // (8 * len(arrays))  # elements per array
+        rng = np.random.default_rng(0)
+        for name in sorted(arrays):
+            flat = arrays[name].reshape(-1)
+            if flat.size > share:
+                pick = np.sort(rng.choice(flat.size, share, replace=False))
+                arrays[name] = flat[pick]
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def main():
@@ -41,7 +86,20 @@ def main():
                              "the framework — Pool(collective=True) "
                              "SPMD fan-out + pool-communicator "
                              "collectives (single-process launch only)")
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="after the timed steps, write what the last "
+                             "timed step produced (its stats and the "
+                             "engine state it left) as DIR/<name>.npy; "
+                             "--mode pool only sees what the workers "
+                             "return, so there it is the per-rank stats "
+                             "and theta checksum, a much coarser record")
+    parser.add_argument("--full", action="store_true",
+                        help="also run the measurements beyond the "
+                             "headline figure (none exist today: same as "
+                             "a plain run)")
     args = parser.parse_args()
+    if args.steps < 1:
+        parser.error("--steps must be >= 1")
     if args.pop_per_gpu is None:
         # Big shards are the MI355X-first choice (288 GB HBM, fixed costs
         # amortize, collectives stay large); per-GPU work is fixed as N
@@ -119,7 +177,7 @@ def main():
     sync()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        engine.step(iteration=args.warmup + i)
+        stats = engine.step(iteration=args.warmup + i)
     if ctx is not None:
         ctx.barrier()
     sync()
@@ -135,6 +193,18 @@ def main():
     rollouts_per_step = cfg.pop_per_gpu * world * cfg.envs_per_member
     value = rollouts_per_step * args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1000.0
+
+    if args.dump_outputs and rank == 0:
+        # what a caller of step() holds after the last timed step: the
+        # returned stats and the engine state, as rank 0 sees them (every
+        # rank applies the same all-reduced update)
+        arrays = {
+            name: t.numpy()
+            for name, t in engine.state_dict().items()
+            if isinstance(t, torch.Tensor)
+        }
+        arrays["stats"] = stats_array(stats)
+        dump_outputs(args.dump_outputs, arrays)
 
     if rank == 0:
         print(json.dumps({
@@ -199,6 +269,15 @@ def bench_through_pool(args):
     envs = 64 if args.model == "mlp" else 16
     rollouts_per_step = args.pop_per_gpu * args.gpus * envs
     value = rollouts_per_step * args.steps / elapsed
+    if args.dump_outputs:
+        # run_on_all hands the caller one stats dict per rank
+        import numpy as np
+
+        dump_outputs(args.dump_outputs, {
+            "stats": np.stack([stats_array(r) for r in per_rank]),
+            "theta_sum": np.array([r["theta_sum"] for r in per_rank],
+                                  dtype=np.float64),
+        })
     print(_json.dumps({
         "metric": "es_rollouts_per_sec",
         "value": value,

@@ -17,12 +17,15 @@ namespace py = pybind11;
 
 #define NPARAMS_HOST 4610
 #define ENVS_HOST 64
+#define OBS_HOST 4
 
 extern "C" __global__ void es_rollout_mlp(
     const float*, float, uint32_t, uint32_t, int, int, const float*,
-    const float*, const float*, const float*, float*, float*);
+    const float*, const float*, const float*, float*, float*, float*);
+extern "C" __global__ void obs_stat_reduce(const float*, int, float*);
 extern "C" __global__ void es_grad(const float*, int, int, int, uint32_t,
                                    uint32_t, int, float*);
+extern "C" __global__ void es_grad_reduce(const float*, int, int, float*);
 extern "C" __global__ void centered_rank(const float*, int, float*);
 extern "C" __global__ void rank_pack_keys(const float*, int, unsigned*,
                                           unsigned*);
@@ -68,33 +71,54 @@ static void launch_rollout(uintptr_t theta, double sigma, uint32_t seed,
                            uint32_t iter, int horizon, int member_offset,
                            int pop_shard, uintptr_t obs_mu, uintptr_t obs_nu,
                            uintptr_t env_A, uintptr_t env_B,
-                           uintptr_t fitness, uintptr_t obs_stat,
-                           uintptr_t stream) {
+                           uintptr_t fitness, uintptr_t obs_stat_part,
+                           uintptr_t obs_stat, uintptr_t stream) {
+  if (pop_shard <= 0) return;
   hipLaunchKernelGGL(es_rollout_mlp, dim3(pop_shard), dim3(256), 0,
                      (hipStream_t)stream, (const float*)theta, (float)sigma,
                      seed, iter, horizon, member_offset,
                      (const float*)obs_mu, (const float*)obs_nu,
                      (const float*)env_A, (const float*)env_B,
-                     (float*)fitness, (float*)obs_stat);
+                     (float*)fitness, (float*)obs_stat_part,
+                     (float*)obs_stat);
   check(hipGetLastError(), "es_rollout_mlp launch");
+  // obs_stat_part is [pop_shard][2*OBS]; one block per stat column
+  hipLaunchKernelGGL(obs_stat_reduce, dim3(2 * OBS_HOST), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)obs_stat_part,
+                     pop_shard, (float*)obs_stat);
+  check(hipGetLastError(), "obs_stat_reduce launch");
+}
+
+// Pair-range split of es_grad: enough workgroups to fill the chip (fewer
+// chunks for large nparams — bx already provides parallelism).
+static int grad_chunks(int pairs, int nparams) {
+  const int bx = ((nparams + 3) / 4 + 255) / 256;
+  return pairs < 64 ? 1 : (bx >= 32 ? 4 : 32);
 }
 
 static void launch_grad(uintptr_t wpair, int pair_begin, int pair_end,
                         uint32_t seed, uint32_t iter, int nparams,
-                        uintptr_t grad, uintptr_t stream) {
+                        uintptr_t grad_part, uintptr_t grad,
+                        uintptr_t stream) {
   const int jblocks = (nparams + 3) / 4;
   const int bx = (jblocks + 255) / 256;
   int pairs = pair_end - pair_begin;
   if (pairs <= 0) return;
-  // Split pairs so enough workgroups exist to fill the chip (fewer
-  // chunks for large nparams — bx already provides parallelism).
-  int chunks = pairs < 64 ? 1 : (bx >= 32 ? 4 : 32);
+  // grad_part holds grad_chunks(pairs, nparams) * nparams floats
+  const int chunks = grad_chunks(pairs, nparams);
   int per_chunk = (pairs + chunks - 1) / chunks;
   hipLaunchKernelGGL(es_grad, dim3(bx, chunks), dim3(256), 0,
                      (hipStream_t)stream, (const float*)wpair, pair_begin,
                      pair_end, per_chunk, seed, iter, nparams,
-                     (float*)grad);
+                     chunks == 1 ? (float*)grad : (float*)grad_part);
   check(hipGetLastError(), "es_grad launch");
+  if (chunks > 1) {
+    hipLaunchKernelGGL(es_grad_reduce, dim3((nparams + 255) / 256),
+                       dim3(256), 0, (hipStream_t)stream,
+                       (const float*)grad_part, chunks, nparams,
+                       (float*)grad);
+    check(hipGetLastError(), "es_grad_reduce launch");
+  }
 }
 
 static void launch_centered_rank(uintptr_t f, int n, uintptr_t out,
@@ -254,11 +278,14 @@ PYBIND11_MODULE(_ops, m) {
         py::arg("sigma"), py::arg("seed"), py::arg("iter"),
         py::arg("horizon"), py::arg("member_offset"), py::arg("pop_shard"),
         py::arg("obs_mu"), py::arg("obs_nu"), py::arg("env_A"),
-        py::arg("env_B"), py::arg("fitness"), py::arg("obs_stat"),
-        py::arg("stream"));
+        py::arg("env_B"), py::arg("fitness"), py::arg("obs_stat_part"),
+        py::arg("obs_stat"), py::arg("stream"));
   m.def("es_grad", &launch_grad, py::arg("wpair"), py::arg("pair_begin"),
         py::arg("pair_end"), py::arg("seed"), py::arg("iter"),
-        py::arg("nparams"), py::arg("grad"), py::arg("stream"));
+        py::arg("nparams"), py::arg("grad_part"), py::arg("grad"),
+        py::arg("stream"));
+  m.def("es_grad_chunks", &grad_chunks, py::arg("pairs"),
+        py::arg("nparams"));
   m.def("centered_rank", &launch_centered_rank, py::arg("f"), py::arg("n"),
         py::arg("out"), py::arg("stream"));
   m.def("centered_rank_sorted_workspace", &centered_rank_sorted_workspace,

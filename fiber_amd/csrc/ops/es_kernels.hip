@@ -259,6 +259,7 @@ es_rollout_mlp(const float* __restrict__ theta, float sigma, uint32_t seed,
                const float* __restrict__ env_A,   // [OBS][OBS]
                const float* __restrict__ env_B,   // [OBS]
                float* __restrict__ fitness,       // [pop_shard]
+               float* __restrict__ obs_stat_part, // [pop_shard][2*OBS]
                float* __restrict__ obs_stat_out)  // [2*OBS+1]
 {
   __shared__ RolloutLds L;
@@ -380,8 +381,17 @@ es_rollout_mlp(const float* __restrict__ theta, float sigma, uint32_t seed,
   // reward partials: 4 per env (one per dim-owner thread), staged via
   // lpart then wave-0 shuffle-reduced — deterministic order.
   L.lpart[dd][env][0] = raccp;
-  atomicAdd(&L.ostat[dd], psum);
-  atomicAdd(&L.ostat[OBS + dd], psq);
+  // obs-stat partials: wave w holds dim w for all 64 envs, so a fixed
+  // shuffle tree gives the same sum every run (no float atomics).
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    psum += __shfl_down(psum, off, 64);
+    psq += __shfl_down(psq, off, 64);
+  }
+  if (lane == 0) {
+    L.ostat[dd] = psum;
+    L.ostat[OBS + dd] = psq;
+  }
   __syncthreads();
   if (wave == 0) {
     float r = L.lpart[0][lane][0] + L.lpart[1][lane][0] +
@@ -390,9 +400,33 @@ es_rollout_mlp(const float* __restrict__ theta, float sigma, uint32_t seed,
     for (int off = 32; off > 0; off >>= 1) r += __shfl_down(r, off, 64);
     if (lane == 0) fitness[blockIdx.x] = r / (float)ENVS;
   }
-  if (tid < 2 * OBS) atomicAdd(&obs_stat_out[tid], L.ostat[tid]);
+  // per-member partials; obs_stat_reduce sums them in a fixed order
+  if (tid < 2 * OBS)
+    obs_stat_part[(size_t)blockIdx.x * (2 * OBS) + tid] = L.ostat[tid];
+  // every block adds the same value, so the order cannot change the sum
   if (tid == 0)
     atomicAdd(&obs_stat_out[2 * OBS], (float)(ENVS * horizon));
+}
+
+// obs_stat_out[c] = sum over members of part[m][c], c < 2*OBS: one block
+// per column, strided partials then a fixed LDS tree — run-to-run
+// reproducible, unlike float atomics from 32k blocks.
+extern "C" __global__ void __launch_bounds__(256)
+obs_stat_reduce(const float* __restrict__ part, int nmembers,
+                float* __restrict__ obs_stat_out) {
+  __shared__ float red[256];
+  const int tid = threadIdx.x;
+  const int col = blockIdx.x;  // grid is exactly 2*OBS blocks
+  float acc = 0.f;
+  for (int m = tid; m < nmembers; m += 256)
+    acc += part[(size_t)m * (2 * OBS) + col];
+  red[tid] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) obs_stat_out[col] = red[0];
 }
 
 // ---------------------------------------------------------------------------
@@ -403,7 +437,7 @@ extern "C" __global__ void es_grad(const float* __restrict__ wpair,
                                    int pair_begin, int pair_end,
                                    int pairs_per_chunk, uint32_t seed,
                                    uint32_t iter, int nparams,
-                                   float* __restrict__ grad) {
+                                   float* __restrict__ out) {
   const int jb = blockIdx.x * blockDim.x + threadIdx.x;
   if (jb * 4 >= nparams) return;
   const int chunk_begin = pair_begin + blockIdx.y * pairs_per_chunk;
@@ -418,11 +452,26 @@ extern "C" __global__ void es_grad(const float* __restrict__ wpair,
 #pragma unroll
     for (int u = 0; u < 4; ++u) acc[u] += w * z[u];
   }
+  // Each (chunk, j) is written by exactly one thread.  With one chunk
+  // `out` is the gradient itself; otherwise it is the [chunks][nparams]
+  // partial buffer that es_grad_reduce sums in chunk order, so the result
+  // is the same every run (no float atomics).
+  float* __restrict__ row = out + (size_t)blockIdx.y * nparams;
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const int j = jb * 4 + u;
-    if (j < nparams && (acc[u] != 0.f)) atomicAdd(&grad[j], acc[u]);
+    if (j < nparams) row[j] = acc[u];
   }
+}
+
+extern "C" __global__ void es_grad_reduce(const float* __restrict__ part,
+                                          int chunks, int nparams,
+                                          float* __restrict__ grad) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= nparams) return;
+  float acc = 0.f;
+  for (int c = 0; c < chunks; ++c) acc += part[(size_t)c * nparams + j];
+  grad[j] = acc;
 }
 
 // ---------------------------------------------------------------------------

@@ -47,6 +47,15 @@ def _check(t, name, dtype=torch.float32, device=True):
     return t
 
 
+def _partial_buffer(device, numel):
+    """Scratch for per-block partial sums that a second kernel reduces in a
+    fixed order (what keeps the reductions reproducible run to run).
+    Allocated per call on the current stream, the one both kernels are
+    launched on, so the caching allocator only hands the block out again
+    after them in stream order: safe with several engines or streams."""
+    return torch.empty(numel, dtype=torch.float32, device=device)
+
+
 def es_rollout_mlp(theta, sigma, seed, iteration, horizon, member_offset,
                    pop_shard, obs_mu, obs_nu, env_A, env_B):
     """One persistent-kernel launch rolling out ``pop_shard`` perturbed
@@ -59,6 +68,7 @@ def es_rollout_mlp(theta, sigma, seed, iteration, horizon, member_offset,
                           device=theta.device)
     obs_stat = torch.zeros(2 * OBS_DIM + 1, dtype=torch.float32,
                            device=theta.device)
+    part = _partial_buffer(theta.device, int(pop_shard) * 2 * OBS_DIM)
     ops.es_rollout_mlp(
         theta.data_ptr(), float(sigma), int(seed) & 0xFFFFFFFF,
         int(iteration) & 0xFFFFFFFF, int(horizon), int(member_offset),
@@ -66,7 +76,7 @@ def es_rollout_mlp(theta, sigma, seed, iteration, horizon, member_offset,
         _check(obs_nu, "obs_nu").data_ptr(),
         _check(env_A, "env_A").data_ptr(),
         _check(env_B, "env_B").data_ptr(), fitness.data_ptr(),
-        obs_stat.data_ptr(), _stream())
+        part.data_ptr(), obs_stat.data_ptr(), _stream())
     return fitness, obs_stat
 
 
@@ -78,9 +88,12 @@ def es_grad(wpair, pair_begin, pair_end, seed, iteration, device,
     if nparams is None:
         nparams = NPARAMS
     grad = torch.zeros(nparams, dtype=torch.float32, device=device)
+    chunks = ops.es_grad_chunks(int(pair_end) - int(pair_begin),
+                                int(nparams))
+    part = _partial_buffer(grad.device, chunks * int(nparams))
     ops.es_grad(wpair.data_ptr(), int(pair_begin), int(pair_end),
                 int(seed) & 0xFFFFFFFF, int(iteration) & 0xFFFFFFFF,
-                int(nparams), grad.data_ptr(), _stream())
+                int(nparams), part.data_ptr(), grad.data_ptr(), _stream())
     return grad
 
 

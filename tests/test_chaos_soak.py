@@ -33,16 +33,43 @@ def _soak_seconds(default):
     )
 
 
+def _worker_start_latency():
+    """Seconds from spawning one worker to its first delivered result on
+    this machine (interpreter start + imports + dial-back + one chunk)."""
+    pool = ResilientZPool(processes=1)
+    try:
+        t0 = time.monotonic()
+        assert pool.map(_churn_task, [0]) == [0]
+        return time.monotonic() - t0
+    finally:
+        pool.terminate()
+        pool.join()
+
+
 class TestPoolChurn:
     def test_pool_survives_continuous_worker_murder(self):
         duration = _soak_seconds(20.0)
+        # The pool respawns workers one at a time, so it can only make
+        # progress while kills arrive slower than one worker can start.
+        # Kill faster than that and the population collapses to a single
+        # newborn worker that dies before its first result; ten of those
+        # in a row is (correctly) reported as a crash loop, which is not
+        # what this test is about.  The nominal 20-120 ms interval (mean
+        # 70 ms) assumes a worker starts in under 35 ms; where it takes
+        # longer the interval is stretched so its mean is twice the
+        # measured start latency.  Kill timing within a worker's life
+        # stays random, so every transport state is still hit.
+        pace = max(1.0, 2.0 * _worker_start_latency() / 0.07)
+        # Keep the pressure: whatever the pace, run long enough for about
+        # 100 kills (unchanged 20 s up to a ~100 ms worker start).
+        duration = max(duration, 100 * 0.07 * pace)
         pool = ResilientZPool(processes=4)
         stop = threading.Event()
         kills = [0]
 
         def killer():
             while not stop.is_set():
-                time.sleep(random.uniform(0.02, 0.12))
+                time.sleep(random.uniform(0.02, 0.12) * pace)
                 with pool._worker_lock:
                     procs = [p for p in pool._workers.values()
                              if p.exitcode is None]

@@ -113,9 +113,18 @@ class TestManyFds:
         """Reference regression (tests/test_popen.py:95-113): process
         management must not depend on select()-able fd numbers < 1024."""
         import os
+        import resource
 
-        fds = [os.open("/dev/null", os.O_RDONLY) for _ in range(1100)]
+        # A login shell's default soft limit is often 1024: lift it to the
+        # hard limit for this test so the 1100 descriptors can exist.
+        soft, hard = resource.getrlimit(resource.RLIMIT_NOFILE)
+        want = 4096 if hard == resource.RLIM_INFINITY else min(4096, hard)
+        if soft != resource.RLIM_INFINITY and soft < want:
+            resource.setrlimit(resource.RLIMIT_NOFILE, (want, hard))
+        fds = []
         try:
+            for _ in range(1100):
+                fds.append(os.open("/dev/null", os.O_RDONLY))
             p = fiber_amd.Process(target=_noop)
             p.start()
             p.join(60)
@@ -123,6 +132,7 @@ class TestManyFds:
         finally:
             for fd in fds:
                 os.close(fd)
+            resource.setrlimit(resource.RLIMIT_NOFILE, (soft, hard))
 
 
 class TestStartFailure:
