@@ -22,6 +22,10 @@ namespace py = pybind11;
 extern "C" __global__ void es_rollout_mlp(
     const float*, float, uint32_t, uint32_t, int, int, const float*,
     const float*, const float*, const float*, float*, float*, float*);
+extern "C" __global__ void es_eval_matrix(const float*, const float*,
+                                          const float*, const float*,
+                                          const float*, uint32_t, uint32_t,
+                                          int, int, float*, float*);
 extern "C" __global__ void obs_stat_reduce(const float*, int, float*);
 extern "C" __global__ void es_grad(const float*, int, int, int, uint32_t,
                                    uint32_t, int, float*);
@@ -87,6 +91,28 @@ static void launch_rollout(uintptr_t theta, double sigma, uint32_t seed,
                      (hipStream_t)stream, (const float*)obs_stat_part,
                      pop_shard, (float*)obs_stat);
   check(hipGetLastError(), "obs_stat_reduce launch");
+}
+
+// K policies x M environments, one workgroup per cell (flattened into
+// grid.x: K*M may exceed the 65535 cap of grid.y).  episodes == 0 skips
+// the per-episode store.
+static void launch_eval_matrix(uintptr_t thetas, uintptr_t obs_mu,
+                               uintptr_t obs_nu, uintptr_t env_A,
+                               uintptr_t env_B, uint32_t seed, uint32_t iter,
+                               int horizon, int K, int M, uintptr_t scores,
+                               uintptr_t episodes, uintptr_t stream) {
+  if (K <= 0 || M <= 0) return;
+  const long long cells = (long long)K * (long long)M;
+  if (cells > 0x7FFFFFFFLL)
+    throw std::runtime_error("es_eval_matrix: K*M exceeds the grid limit");
+  if (horizon < 1)
+    throw std::runtime_error("es_eval_matrix: horizon must be >= 1");
+  hipLaunchKernelGGL(es_eval_matrix, dim3((unsigned)cells), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)thetas,
+                     (const float*)obs_mu, (const float*)obs_nu,
+                     (const float*)env_A, (const float*)env_B, seed, iter,
+                     horizon, M, (float*)scores, (float*)episodes);
+  check(hipGetLastError(), "es_eval_matrix launch");
 }
 
 // Pair-range split of es_grad: enough workgroups to fill the chip (fewer
@@ -280,6 +306,11 @@ PYBIND11_MODULE(_ops, m) {
         py::arg("obs_mu"), py::arg("obs_nu"), py::arg("env_A"),
         py::arg("env_B"), py::arg("fitness"), py::arg("obs_stat_part"),
         py::arg("obs_stat"), py::arg("stream"));
+  m.def("es_eval_matrix", &launch_eval_matrix, py::arg("thetas"),
+        py::arg("obs_mu"), py::arg("obs_nu"), py::arg("env_A"),
+        py::arg("env_B"), py::arg("seed"), py::arg("iter"),
+        py::arg("horizon"), py::arg("K"), py::arg("M"), py::arg("scores"),
+        py::arg("episodes"), py::arg("stream"));
   m.def("es_grad", &launch_grad, py::arg("wpair"), py::arg("pair_begin"),
         py::arg("pair_end"), py::arg("seed"), py::arg("iter"),
         py::arg("nparams"), py::arg("grad_part"), py::arg("grad"),

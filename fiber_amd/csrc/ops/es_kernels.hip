@@ -251,6 +251,160 @@ struct RolloutLds {
   float ostat[2 * OBS + 1];   // sum, sumsq, count
 };
 
+// ---------------------------------------------------------------------------
+// Pieces shared by es_rollout_mlp (perturbed members, obs statistics) and
+// es_eval_matrix (explicit policies, no statistics).  Both kernels inline
+// the SAME functions, so the step arithmetic cannot drift between them:
+// at sigma = 0 the two produce bit-identical returns.  STATS compiles the
+// obs-stat accumulation in (rollout) or out (eval).
+// ---------------------------------------------------------------------------
+
+// Everything in RolloutLds except the policy values: zero the K-padding of
+// W1 (A-side zeros make pad products zero) and of xb, draw the env init
+// state (member-independent: common random numbers from seed, iter), zero
+// the stat accumulators.  The caller fills L.pol and then barriers.
+template <bool STATS>
+__device__ __forceinline__ void rollout_init_lds(RolloutLds& L, int tid,
+                                                 uint32_t seed,
+                                                 uint32_t iter) {
+  for (int idx = tid; idx < HID * (S1 - OBS); idx += blockDim.x) {
+    L.pol.w1[idx / (S1 - OBS)][OBS + idx % (S1 - OBS)] =
+        __float2bfloat16(0.f);
+  }
+  for (int idx = tid; idx < ENVS * (S1 - OBS); idx += blockDim.x) {
+    L.xb[idx / (S1 - OBS)][OBS + idx % (S1 - OBS)] =
+        __float2bfloat16(0.f);
+  }
+  if (tid < ENVS) {
+    float z[4];
+    fam_normal4(seed, iter, (uint32_t)tid, 0u, FAM_TAG_ENV, 0u, z);
+#pragma unroll
+    for (int d = 0; d < OBS; ++d) L.S[0][tid][d] = 0.3f * z[d];
+  }
+  if (STATS) {
+    if (tid < 2 * OBS + 1) L.ostat[tid] = 0.f;
+  }
+}
+
+// The whole horizon for the policy in L.pol: prologue "phase A", then the
+// B / C / D2 step loop, ending on the barrier that closes the last step.
+// Call with L fully initialised and a barrier behind it.  Returns this
+// thread's reward partial; with STATS, psum / psq receive its obs-stat
+// partials.
+//
+// Every phase uses all 256 threads as (env = tid&63, d = tid>>6) —
+// OBS==4 matches the 4 waves exactly.  The thread that owns (env, d)
+// keeps its state component, obs-stat partials AND reward partial in
+// REGISTERS across the whole horizon: phase A is folded into the tail
+// of D2 (4 barriers per step), the fitness path stays deterministic
+// (register partials, no float atomics), and only the cross-dim env
+// state round-trips through LDS (for D2's drive term).
+template <bool STATS>
+__device__ __forceinline__ float rollout_steps(
+    RolloutLds& L, int tid, int horizon, const float* obs_mu,
+    const float* obs_nu,
+    const float* env_A,  // [OBS][OBS]
+    const float* env_B,  // [OBS]
+    float& psum, float& psq) {
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int env = tid & 63;
+  const int dd = tid >> 6;  // 0..3
+  float raccp = 0.f;
+  const float mu_d = obs_mu[dd];
+  const float rstd_d = rsqrtf(obs_nu[dd] + 1e-4f);
+  float eA_d[OBS];
+#pragma unroll
+  for (int e = 0; e < OBS; ++e) eA_d[e] = env_A[dd * OBS + e];
+  const float eB_d = env_B[dd];
+  const float one_if_d0 = (dd == 0) ? 1.f : 0.f;
+  // this lane's w3 slice for the fused logits epilogue: rows
+  // drow..drow+3 of both actions (drow = wave*16 + kgrp*4)
+  float w3r[2 * 4];
+  {
+    const int drow = wave * 16 + (lane >> 4) * 4;
+#pragma unroll
+    for (int ri = 0; ri < 4; ++ri) {
+      w3r[ri] = __bfloat162float(L.pol.w3[0][drow + ri]);
+      w3r[4 + ri] = __bfloat162float(L.pol.w3[1][drow + ri]);
+    }
+  }
+
+  // prologue "phase A" for t=0: stats + normalized obs from the init state
+  {
+    const float s = L.S[0][env][dd];
+    if (STATS) {
+      psum += s;
+      psq += s * s;
+    }
+    float x = (s - mu_d) * rstd_d;
+    L.xb[env][dd] = __float2bfloat16(fminf(5.f, fmaxf(-5.f, x)));
+  }
+
+  for (int t = 0; t < horizon; ++t) {
+    const int cur = t & 1;
+    __syncthreads();
+    // ---- phase B: h1 = tanh(W1 x + b1)  (MFMA, K=32) ------------------
+    mfma_strip_tanh<KPAD, S1, S1, S2, true>(&L.pol.w1[0][0], &L.xb[0][0],
+                                            L.pol.b1, &L.h1[0][0], wave,
+                                            lane);
+    __syncthreads();
+    // ---- phase C: h2 stays in registers; logits fused (MFMA, K=64) ----
+    mfma_strip_logits<HID, S2, S2>(&L.pol.w2[0][0], &L.h1[0][0],
+                                   L.pol.b2, w3r, L.lpart, wave, lane);
+    __syncthreads();
+    // ---- phase D2 (+A of t+1): action, env step, stats, next xb -------
+    {
+      const float l0 = L.pol.b3[0] + L.lpart[0][env][0] +
+                       L.lpart[1][env][0] + L.lpart[2][env][0] +
+                       L.lpart[3][env][0];
+      const float l1 = L.pol.b3[1] + L.lpart[0][env][1] +
+                       L.lpart[1][env][1] + L.lpart[2][env][1] +
+                       L.lpart[3][env][1];
+      const float asign = (l1 > l0) ? 1.f : -1.f;
+      float drive = 0.f;
+#pragma unroll
+      for (int e = 0; e < OBS; ++e) drive += eA_d[e] * L.S[cur][env][e];
+      // a*b + c*d leaves the compiler free to fuse either product into
+      // the add, and the two choices round differently.  The fma is
+      // spelled out (0.97*s rounded, 0.08*tanh fused) so that every
+      // kernel that inlines this loop gets the same bits.
+      const float snew =
+          fmaf(0.08f, fast_tanh(drive), 0.97f * L.S[cur][env][dd]) +
+          0.05f * eB_d * asign;
+      L.S[cur ^ 1][env][dd] = snew;
+      raccp += one_if_d0 - 0.1f * snew * snew;
+      if (t < horizon - 1) {
+        // next step's stats + normalized obs, from the register state
+        if (STATS) {
+          psum += snew;
+          psq += snew * snew;
+        }
+        float x = (snew - mu_d) * rstd_d;
+        L.xb[env][dd] = __float2bfloat16(fminf(5.f, fmaxf(-5.f, x)));
+      }
+    }
+  }
+  __syncthreads();
+  return raccp;
+}
+
+// Reward epilogue, second half: wave 0, after every thread has staged its
+// reward partial in L.lpart[dd][env][0] and the block has barriered.
+// Lane e first forms env e's episode return from its 4 per-dim partials
+// (stored to episodes[e] when that pointer is non-null), then a fixed
+// shuffle tree sums the 64 returns — deterministic order.  The sum is
+// valid in lane 0.
+__device__ __forceinline__ float reward_reduce_wave0(
+    const RolloutLds& L, int lane, float* __restrict__ episodes) {
+  float r = L.lpart[0][lane][0] + L.lpart[1][lane][0] +
+            L.lpart[2][lane][0] + L.lpart[3][lane][0];
+  if (episodes != nullptr) episodes[lane] = r;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) r += __shfl_down(r, off, 64);
+  return r;
+}
+
 extern "C" __global__ void __launch_bounds__(256)
 es_rollout_mlp(const float* __restrict__ theta, float sigma, uint32_t seed,
                uint32_t iter, int horizon, int member_offset,
@@ -281,101 +435,14 @@ es_rollout_mlp(const float* __restrict__ theta, float sigma, uint32_t seed,
       if (j < NPARAMS) store_param(&L.pol, j, theta[j] + sgn * z[u]);
     }
   }
-  // zero the K-padding of W1 (A-side zeros make pad products zero) and xb
-  for (int idx = tid; idx < HID * (S1 - OBS); idx += blockDim.x) {
-    L.pol.w1[idx / (S1 - OBS)][OBS + idx % (S1 - OBS)] =
-        __float2bfloat16(0.f);
-  }
-  for (int idx = tid; idx < ENVS * (S1 - OBS); idx += blockDim.x) {
-    L.xb[idx / (S1 - OBS)][OBS + idx % (S1 - OBS)] =
-        __float2bfloat16(0.f);
-  }
-  // init env state (member-independent: common random numbers), zero accs
-  if (tid < ENVS) {
-    float z[4];
-    fam_normal4(seed, iter, (uint32_t)tid, 0u, FAM_TAG_ENV, 0u, z);
-#pragma unroll
-    for (int d = 0; d < OBS; ++d) L.S[0][tid][d] = 0.3f * z[d];
-  }
-  if (tid < 2 * OBS + 1) L.ostat[tid] = 0.f;
+  rollout_init_lds<true>(L, tid, seed, iter);
   __syncthreads();
 
-  // Every phase below uses all 256 threads as (env = tid&63, d = tid>>6)
-  // — OBS==4 matches the 4 waves exactly.  The thread that owns (env, d)
-  // keeps its state component, obs-stat partials AND reward partial in
-  // REGISTERS across the whole horizon: phase A is folded into the tail
-  // of D2 (4 barriers per step), the fitness path stays deterministic
-  // (register partials, no float atomics), and only the cross-dim env
-  // state round-trips through LDS (for D2's drive term).
   const int env = tid & 63;
   const int dd = tid >> 6;  // 0..3
-  float psum = 0.f, psq = 0.f, raccp = 0.f;
-  const float mu_d = obs_mu[dd];
-  const float rstd_d = rsqrtf(obs_nu[dd] + 1e-4f);
-  float eA_d[OBS];
-#pragma unroll
-  for (int e = 0; e < OBS; ++e) eA_d[e] = env_A[dd * OBS + e];
-  const float eB_d = env_B[dd];
-  const float one_if_d0 = (dd == 0) ? 1.f : 0.f;
-  // this lane's w3 slice for the fused logits epilogue: rows
-  // drow..drow+3 of both actions (drow = wave*16 + kgrp*4)
-  float w3r[2 * 4];
-  {
-    const int drow = wave * 16 + (lane >> 4) * 4;
-#pragma unroll
-    for (int ri = 0; ri < 4; ++ri) {
-      w3r[ri] = __bfloat162float(L.pol.w3[0][drow + ri]);
-      w3r[4 + ri] = __bfloat162float(L.pol.w3[1][drow + ri]);
-    }
-  }
-
-  // prologue "phase A" for t=0: stats + normalized obs from the init state
-  {
-    const float s = L.S[0][env][dd];
-    psum += s;
-    psq += s * s;
-    float x = (s - mu_d) * rstd_d;
-    L.xb[env][dd] = __float2bfloat16(fminf(5.f, fmaxf(-5.f, x)));
-  }
-
-  for (int t = 0; t < horizon; ++t) {
-    const int cur = t & 1;
-    __syncthreads();
-    // ---- phase B: h1 = tanh(W1 x + b1)  (MFMA, K=32) ------------------
-    mfma_strip_tanh<KPAD, S1, S1, S2, true>(&L.pol.w1[0][0], &L.xb[0][0],
-                                            L.pol.b1, &L.h1[0][0], wave,
-                                            lane);
-    __syncthreads();
-    // ---- phase C: h2 stays in registers; logits fused (MFMA, K=64) ----
-    mfma_strip_logits<HID, S2, S2>(&L.pol.w2[0][0], &L.h1[0][0],
-                                   L.pol.b2, w3r, L.lpart, wave, lane);
-    __syncthreads();
-    // ---- phase D2 (+A of t+1): action, env step, stats, next xb -------
-    {
-      const float l0 = L.pol.b3[0] + L.lpart[0][env][0] +
-                       L.lpart[1][env][0] + L.lpart[2][env][0] +
-                       L.lpart[3][env][0];
-      const float l1 = L.pol.b3[1] + L.lpart[0][env][1] +
-                       L.lpart[1][env][1] + L.lpart[2][env][1] +
-                       L.lpart[3][env][1];
-      const float asign = (l1 > l0) ? 1.f : -1.f;
-      float drive = 0.f;
-#pragma unroll
-      for (int e = 0; e < OBS; ++e) drive += eA_d[e] * L.S[cur][env][e];
-      const float snew = 0.97f * L.S[cur][env][dd] +
-                         0.08f * fast_tanh(drive) + 0.05f * eB_d * asign;
-      L.S[cur ^ 1][env][dd] = snew;
-      raccp += one_if_d0 - 0.1f * snew * snew;
-      if (t < horizon - 1) {
-        // next step's stats + normalized obs, from the register state
-        psum += snew;
-        psq += snew * snew;
-        float x = (snew - mu_d) * rstd_d;
-        L.xb[env][dd] = __float2bfloat16(fminf(5.f, fmaxf(-5.f, x)));
-      }
-    }
-  }
-  __syncthreads();
+  float psum = 0.f, psq = 0.f;
+  const float raccp = rollout_steps<true>(L, tid, horizon, obs_mu, obs_nu,
+                                          env_A, env_B, psum, psq);
 
   // ---- epilogue: fitness + obs-stat reductions -------------------------
   // reward partials: 4 per env (one per dim-owner thread), staged via
@@ -394,10 +461,7 @@ es_rollout_mlp(const float* __restrict__ theta, float sigma, uint32_t seed,
   }
   __syncthreads();
   if (wave == 0) {
-    float r = L.lpart[0][lane][0] + L.lpart[1][lane][0] +
-              L.lpart[2][lane][0] + L.lpart[3][lane][0];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) r += __shfl_down(r, off, 64);
+    const float r = reward_reduce_wave0(L, lane, nullptr);
     if (lane == 0) fitness[blockIdx.x] = r / (float)ENVS;
   }
   // per-member partials; obs_stat_reduce sums them in a fixed order
@@ -406,6 +470,50 @@ es_rollout_mlp(const float* __restrict__ theta, float sigma, uint32_t seed,
   // every block adds the same value, so the order cannot change the sum
   if (tid == 0)
     atomicAdd(&obs_stat_out[2 * OBS], (float)(ENVS * horizon));
+}
+
+// K explicit (unperturbed) policies x M environments in one launch: one
+// workgroup per cell.  The cell index is flattened into blockIdx.x
+// (k = cell / M, m = cell % M) because gridDim.y stops at 65535 and K*M
+// does not.  theta_k goes straight into LDS — no Philox, no add — and
+// each policy brings its own obs normaliser; the env states and the
+// step loop are es_rollout_mlp's (common random numbers from seed,
+// iter), so scores[k][m] is bit-identical to that kernel's fitness for
+// theta_k at sigma = 0.  No obs statistics, no atomics.
+extern "C" __global__ void __launch_bounds__(256)
+es_eval_matrix(const float* __restrict__ thetas,  // [K][NPARAMS]
+               const float* __restrict__ obs_mu,  // [K][OBS]
+               const float* __restrict__ obs_nu,  // [K][OBS]
+               const float* __restrict__ env_A,   // [M][OBS][OBS]
+               const float* __restrict__ env_B,   // [M][OBS]
+               uint32_t seed, uint32_t iter, int horizon, int M,
+               float* __restrict__ scores,        // [K][M]
+               float* __restrict__ episodes)      // [K][M][ENVS] or null
+{
+  __shared__ RolloutLds L;
+  const int tid = threadIdx.x;
+  const size_t cell = blockIdx.x;
+  const size_t k = cell / (size_t)M;
+  const size_t m = cell % (size_t)M;
+
+  const float* __restrict__ theta = thetas + k * NPARAMS;
+  for (int j = tid; j < NPARAMS; j += blockDim.x)
+    store_param(&L.pol, j, theta[j]);
+  rollout_init_lds<false>(L, tid, seed, iter);
+  __syncthreads();
+
+  float psum = 0.f, psq = 0.f;  // unused: STATS=false compiles them out
+  const float raccp = rollout_steps<false>(
+      L, tid, horizon, obs_mu + k * OBS, obs_nu + k * OBS,
+      env_A + m * (OBS * OBS), env_B + m * OBS, psum, psq);
+
+  L.lpart[tid >> 6][tid & 63][0] = raccp;
+  __syncthreads();
+  if (tid < 64) {
+    const float r = reward_reduce_wave0(
+        L, tid, episodes != nullptr ? episodes + cell * ENVS : nullptr);
+    if (tid == 0) scores[cell] = r / (float)ENVS;
+  }
 }
 
 // obs_stat_out[c] = sum over members of part[m][c], c < 2*OBS: one block

@@ -1,1 +1,12 @@
-from .engine import ESConfig, ESEngine, init_theta, make_env_params  # noqa: F401
+from .engine import (  # noqa: F401
+    ESConfig,
+    ESEngine,
+    eval_matrix_reference,
+    init_theta,
+    make_env_params,
+)
+from .poet import (  # noqa: F401
+    apply_transfers,
+    select_transfers,
+    transfer_matrix,
+)

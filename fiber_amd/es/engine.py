@@ -61,7 +61,8 @@ def init_theta(seed, device):
 
 
 class ESEngine:
-    def __init__(self, config: ESConfig, ctx=None, device=None):
+    def __init__(self, config: ESConfig, ctx=None, device=None,
+                 env_params=None):
         self.cfg = config
         self.ctx = ctx  # fiber_amd.ring.RingContext or None
         self.rank = ctx.rank if ctx else 0
@@ -78,7 +79,24 @@ class ESEngine:
         self.adam_v = torch.zeros_like(self.theta)
         self.t_step = 0
 
-        self.env_A, self.env_B = make_env_params(config.seed, device)
+        # env_params = (env_A[4][4], env_B[4]) puts the engine on a given
+        # environment (a POET pair); the default is the one derived from
+        # the seed.  The environment is not part of state_dict().
+        if env_params is None:
+            self.env_A, self.env_B = make_env_params(config.seed, device)
+        else:
+            env_A, env_B = env_params
+            n = config.obs_dim
+            if tuple(env_A.shape) != (n, n) or tuple(env_B.shape) != (n,):
+                raise ValueError(
+                    "env_params must be (env_A[%d][%d], env_B[%d])"
+                    % (n, n, n))
+            # own copies: mutating the caller's tensors later must not
+            # move this engine's environment
+            self.env_A = env_A.detach().to(
+                device=device, dtype=torch.float32, copy=True).contiguous()
+            self.env_B = env_B.detach().to(
+                device=device, dtype=torch.float32, copy=True).contiguous()
         self.obs_sum = torch.zeros(config.obs_dim, device=device)
         self.obs_sumsq = torch.zeros(config.obs_dim, device=device)
         self.obs_count = torch.zeros(1, device=device)
@@ -162,6 +180,27 @@ class ESEngine:
             "env_steps": self.pop_total * cfg.envs_per_member * cfg.horizon,
         }
 
+    # -- score the current policy -----------------------------------------
+    def evaluate(self, horizon=None, iteration=None, return_episodes=False):
+        """Mean return of the current, unperturbed theta on this engine's
+        environment with its current obs normaliser: one es_eval_matrix
+        launch with K = M = 1.  The 64 episodes start from the states that
+        step(iteration) uses.  Returns a 0-dim device tensor, plus the 64
+        episode returns if asked.  Changes nothing in the engine."""
+        if horizon is None:
+            horizon = self.cfg.horizon
+        if iteration is None:
+            iteration = self.t_step
+        out = ops.es_eval_matrix(
+            self.theta.unsqueeze(0), self.obs_mu.unsqueeze(0),
+            self.obs_nu.unsqueeze(0), self.env_A.unsqueeze(0),
+            self.env_B.unsqueeze(0), self.cfg.seed, iteration, horizon,
+            return_episodes=return_episodes)
+        if return_episodes:
+            scores, episodes = out
+            return scores.reshape(()), episodes.reshape(-1)
+        return out.reshape(())
+
     # -- checkpoint / resume ----------------------------------------------
     # (the reference has no checkpointing — SURVEY §5; this is additive.)
     def state_dict(self):
@@ -207,15 +246,57 @@ class ESEngine:
 # ---------------------------------------------------------------------------
 
 
+def _bf(t):
+    return t.to(torch.bfloat16).to(torch.float32)
+
+
+def _reference_policy(th):
+    """Split a flat fp32 theta into the layers as the kernel holds them:
+    weights rounded to bf16, biases fp32."""
+    w1 = _bf(th[:256].view(64, 4))
+    b1 = th[256:320]
+    w2 = _bf(th[320:4416].view(64, 64))
+    b2 = th[4416:4480]
+    w3 = _bf(th[4480:4608].view(2, 64))
+    b3 = th[4608:4610]
+    return w1, b1, w2, b2, w3, b3
+
+
+def _reference_step(s, policy, obs_mu, rstd, env_A, env_B):
+    """One env step for all episodes of one (policy, env) pair: s[E][4] ->
+    the next state.  Shared by rollout_reference and
+    eval_matrix_reference, as the step loop is shared by the two kernels."""
+    w1, b1, w2, b2, w3, b3 = policy
+    x = ((s - obs_mu) * rstd).clamp(-5, 5)
+    h1 = _bf(torch.tanh(_bf(x) @ w1.T + b1))
+    # layer-2 activations stay fp32 in the kernel (fused-logits
+    # epilogue, no bf16 store)
+    h2 = torch.tanh(h1 @ w2.T + b2)
+    logits = h2 @ w3.T + b3
+    asign = torch.where(logits[:, 1] > logits[:, 0], 1.0, -1.0)
+    drive = torch.tanh(s @ env_A.T)
+    return 0.97 * s + 0.08 * drive + 0.05 * env_B * asign[:, None]
+
+
+def _reference_episodes(th, s0, horizon, obs_mu, obs_nu, env_A, env_B):
+    """Per-episode returns racc[E] of policy th from the init states s0."""
+    policy = _reference_policy(th)
+    s = s0.clone()
+    racc = torch.zeros(s0.shape[0])
+    rstd = torch.rsqrt(obs_nu + 1e-4)
+    for _ in range(horizon):
+        snew = _reference_step(s, policy, obs_mu, rstd, env_A, env_B)
+        racc += 1.0 - 0.1 * (snew * snew).sum(dim=1)
+        s = snew
+    return racc
+
+
 def rollout_reference(theta, sigma, seed, iteration, horizon, members,
                       obs_mu, obs_nu, env_A, env_B):
     """Returns fitness[len(members)] computed on CPU in fp32 (+bf16
     rounding at the same points as the kernel)."""
 
     from . import philox_ref
-
-    def bf(t):
-        return t.to(torch.bfloat16).to(torch.float32)
 
     theta = theta.detach().cpu()
     obs_mu = obs_mu.detach().cpu()
@@ -235,27 +316,33 @@ def rollout_reference(theta, sigma, seed, iteration, horizon, members,
             philox_ref.noise_for_pair(seed, iteration, pair, ops.NPARAMS)
         )
         th = theta + sgn * eps
-        w1 = bf(th[:256].view(64, 4))
-        b1 = th[256:320]
-        w2 = bf(th[320:4416].view(64, 64))
-        b2 = th[4416:4480]
-        w3 = bf(th[4480:4608].view(2, 64))
-        b3 = th[4608:4610]
-
-        s = s0.clone()
-        racc = torch.zeros(E)
-        rstd = torch.rsqrt(obs_nu + 1e-4)
-        for _ in range(horizon):
-            x = ((s - obs_mu) * rstd).clamp(-5, 5)
-            h1 = bf(torch.tanh(bf(x) @ w1.T + b1))
-            # layer-2 activations stay fp32 in the kernel (fused-logits
-            # epilogue, no bf16 store)
-            h2 = torch.tanh(h1 @ w2.T + b2)
-            logits = h2 @ w3.T + b3
-            asign = torch.where(logits[:, 1] > logits[:, 0], 1.0, -1.0)
-            drive = torch.tanh(s @ env_A.T)
-            snew = 0.97 * s + 0.08 * drive + 0.05 * env_B * asign[:, None]
-            racc += 1.0 - 0.1 * (snew * snew).sum(dim=1)
-            s = snew
+        racc = _reference_episodes(th, s0, horizon, obs_mu, obs_nu, env_A,
+                                   env_B)
         fitness.append(float(racc.mean()))
     return torch.tensor(fitness)
+
+
+def eval_matrix_reference(thetas, obs_mu, obs_nu, env_A, env_B, seed,
+                          iteration, horizon):
+    """CPU oracle of ops.es_eval_matrix: episodes[K][M][64] in fp32 (+bf16
+    rounding at the kernel's rounding points) for K unperturbed policies,
+    each with its own normaliser, on M environments.  The scores are its
+    mean over the last axis."""
+
+    from . import philox_ref
+
+    thetas = thetas.detach().cpu()
+    obs_mu = obs_mu.detach().cpu()
+    obs_nu = obs_nu.detach().cpu()
+    env_A = env_A.detach().cpu()
+    env_B = env_B.detach().cpu()
+    E = ops.ENVS_PER_MEMBER
+    K, M = thetas.shape[0], env_A.shape[0]
+    s0 = torch.from_numpy(philox_ref.env_init_state(seed, iteration, E))
+    episodes = torch.empty(K, M, E)
+    for k in range(K):
+        for m in range(M):
+            episodes[k, m] = _reference_episodes(
+                thetas[k], s0, horizon, obs_mu[k], obs_nu[k], env_A[m],
+                env_B[m])
+    return episodes

@@ -80,6 +80,65 @@ def es_rollout_mlp(theta, sigma, seed, iteration, horizon, member_offset,
     return fitness, obs_stat
 
 
+def es_eval_matrix(thetas, obs_mu, obs_nu, env_A, env_B, seed, iteration,
+                   horizon, return_episodes=False):
+    """Roll out K explicit (unperturbed) policies on M environments in one
+    launch, one workgroup per (policy, environment) cell.
+
+    ``thetas[K][NPARAMS]``, ``obs_mu[K][4]`` / ``obs_nu[K][4]`` (each
+    policy owns its normaliser), ``env_A[M][4][4]``, ``env_B[M][4]``.  The
+    64 episodes per cell start from the same states as ``es_rollout_mlp``
+    at (seed, iteration) and run the same step loop, so ``scores[k][m]``
+    is bit-identical to that kernel's fitness for ``thetas[k]`` at
+    ``sigma=0``.  Returns ``scores[K][M]`` (mean return over the 64
+    episodes), or ``(scores, episodes[K][M][64])``.
+
+    Every argument is validated before anything is launched: TypeError
+    for dtype, device or contiguity, ValueError for shape or horizon."""
+    ops = _require_ops()
+    named = (("thetas", thetas), ("obs_mu", obs_mu), ("obs_nu", obs_nu),
+             ("env_A", env_A), ("env_B", env_B))
+    for name, t in named:
+        _check(t, name)
+        if t.device != thetas.device:
+            raise TypeError("%s is on %s, thetas on %s"
+                            % (name, t.device, thetas.device))
+    if thetas.dim() != 2 or thetas.shape[1] != NPARAMS:
+        raise ValueError("thetas must be [K, %d], got %s"
+                         % (NPARAMS, tuple(thetas.shape)))
+    K = thetas.shape[0]
+    if env_A.dim() != 3 or tuple(env_A.shape[1:]) != (OBS_DIM, OBS_DIM):
+        raise ValueError("env_A must be [M, %d, %d], got %s"
+                         % (OBS_DIM, OBS_DIM, tuple(env_A.shape)))
+    M = env_A.shape[0]
+    for name, t, want in (("obs_mu", obs_mu, (K, OBS_DIM)),
+                          ("obs_nu", obs_nu, (K, OBS_DIM)),
+                          ("env_B", env_B, (M, OBS_DIM))):
+        if tuple(t.shape) != want:
+            raise ValueError("%s must be %s, got %s"
+                             % (name, list(want), tuple(t.shape)))
+    horizon = int(horizon)
+    if horizon < 1:
+        raise ValueError("horizon must be >= 1, got %d" % horizon)
+    if K * M >= 2 ** 31:
+        raise ValueError("K*M = %d exceeds the launch grid" % (K * M))
+    device = thetas.device
+    scores = torch.empty(K, M, dtype=torch.float32, device=device)
+    episodes = None
+    if return_episodes:
+        episodes = torch.empty(K, M, ENVS_PER_MEMBER, dtype=torch.float32,
+                               device=device)
+    with torch.cuda.device(device):
+        ops.es_eval_matrix(
+            thetas.data_ptr(), obs_mu.data_ptr(), obs_nu.data_ptr(),
+            env_A.data_ptr(), env_B.data_ptr(), int(seed) & 0xFFFFFFFF,
+            int(iteration) & 0xFFFFFFFF, horizon, K, M, scores.data_ptr(),
+            episodes.data_ptr() if return_episodes else 0, _stream())
+    if return_episodes:
+        return scores, episodes
+    return scores
+
+
 def es_grad(wpair, pair_begin, pair_end, seed, iteration, device,
             nparams=None):
     """Noise-weighted gradient over local pairs; eps regenerated on-chip."""
