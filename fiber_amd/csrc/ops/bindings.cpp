@@ -257,12 +257,12 @@ static void launch_conv_noisegen(uint32_t seed, uintptr_t iterp, uint32_t t,
   check(hipGetLastError(), "conv_noisegen launch");
 }
 
-static void launch_conv_forward(uintptr_t wpert, uintptr_t w3_fp8,
-                                uintptr_t w1_fp8, uintptr_t state,
-                                uintptr_t gtab, uintptr_t znoise,
-                                uintptr_t act1, uintptr_t act2,
-                                uintptr_t act3, int nmembers,
-                                uintptr_t stream) {
+// One launcher per MFMA layer, so the layer tests can drive each kernel
+// on its own; conv_forward is the three of them in order.
+static void launch_conv_layer1(uintptr_t wpert, uintptr_t w1_fp8,
+                               uintptr_t state, uintptr_t gtab,
+                               uintptr_t znoise, uintptr_t act1,
+                               int nmembers, uintptr_t stream) {
   const int nenv = nmembers * 16;
   hipLaunchKernelGGL(conv_layer1, dim3(nenv), dim3(256), 0,
                      (hipStream_t)stream, (const __hip_bfloat16*)wpert,
@@ -271,17 +271,40 @@ static void launch_conv_forward(uintptr_t wpert, uintptr_t w3_fp8,
                      (const unsigned char*)znoise, nenv,
                      (__hip_bfloat16*)act1);
   check(hipGetLastError(), "conv_layer1 launch");
+}
+
+static void launch_conv_layer2(uintptr_t wpert, uintptr_t act1,
+                               uintptr_t act2, int nmembers,
+                               uintptr_t stream) {
+  const int nenv = nmembers * 16;
   hipLaunchKernelGGL(conv_layer2, dim3(nenv), dim3(256), 0,
                      (hipStream_t)stream, (const __hip_bfloat16*)wpert,
                      (const __hip_bfloat16*)act1, nenv,
                      (unsigned char*)act2);
   check(hipGetLastError(), "conv_layer2 launch");
+}
+
+static void launch_conv_fc(uintptr_t wpert, uintptr_t w3_fp8,
+                           uintptr_t act2, uintptr_t act3, int nmembers,
+                           uintptr_t stream) {
   hipLaunchKernelGGL(conv_fc, dim3(nmembers, 4), dim3(256), 0,
                      (hipStream_t)stream, (const __hip_bfloat16*)wpert,
                      (const unsigned char*)w3_fp8,
                      (const unsigned char*)act2, nmembers,
                      (__hip_bfloat16*)act3);
   check(hipGetLastError(), "conv_fc launch");
+}
+
+static void launch_conv_forward(uintptr_t wpert, uintptr_t w3_fp8,
+                                uintptr_t w1_fp8, uintptr_t state,
+                                uintptr_t gtab, uintptr_t znoise,
+                                uintptr_t act1, uintptr_t act2,
+                                uintptr_t act3, int nmembers,
+                                uintptr_t stream) {
+  launch_conv_layer1(wpert, w1_fp8, state, gtab, znoise, act1, nmembers,
+                     stream);
+  launch_conv_layer2(wpert, act1, act2, nmembers, stream);
+  launch_conv_fc(wpert, w3_fp8, act2, act3, nmembers, stream);
 }
 
 static void launch_conv_head_env(uintptr_t wpert, uintptr_t act3,
@@ -347,6 +370,16 @@ PYBIND11_MODULE(_ops, m) {
   m.def("conv_forward", &launch_conv_forward, py::arg("wpert"),
         py::arg("w3_fp8"), py::arg("w1_fp8"), py::arg("state"),
         py::arg("gtab"), py::arg("znoise"), py::arg("act1"),
+        py::arg("act2"), py::arg("act3"), py::arg("nmembers"),
+        py::arg("stream"));
+  m.def("conv_layer1", &launch_conv_layer1, py::arg("wpert"),
+        py::arg("w1_fp8"), py::arg("state"), py::arg("gtab"),
+        py::arg("znoise"), py::arg("act1"), py::arg("nmembers"),
+        py::arg("stream"));
+  m.def("conv_layer2", &launch_conv_layer2, py::arg("wpert"),
+        py::arg("act1"), py::arg("act2"), py::arg("nmembers"),
+        py::arg("stream"));
+  m.def("conv_fc", &launch_conv_fc, py::arg("wpert"), py::arg("w3_fp8"),
         py::arg("act2"), py::arg("act3"), py::arg("nmembers"),
         py::arg("stream"));
   m.def("conv_head_env", &launch_conv_head_env, py::arg("wpert"),

@@ -302,6 +302,10 @@ class ConvESEngine:
 
 def conv_rollout_reference(theta, sigma, seed, iteration, horizon, members,
                            env_A, env_B, gtab):
+    """Whole-rollout fitness in fp32.  It sees the policy only through
+    argmax -> force, so it is a coarse check; the per-layer fp64
+    references and the per-element criterion live in conv_reference.py
+    (tests/gpu/test_conv_layers.py)."""
     import numpy as np
 
     from . import philox_ref
