@@ -33,6 +33,7 @@
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 // tanh via the hardware transcendental unit (v_exp_f32):
 // tanh(x) = 1 - 2/(e^{2x}+1).  ~6 VALU slots vs ~40 for libm tanhf —
@@ -40,28 +41,45 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 // PMC profile (profiles/r01_rollout_pmc.md) showed the libm version made
 // the kernel VALU-bound at 3.6% MfmaUtil.  exp overflow saturates
 // correctly (inf -> tanh=1).
+//
+// e^{2x} = exp2(x * 2*log2(e)).  __expf(2x) lowers to v_mul(2x, log2e) +
+// v_exp_f32; the doubling is folded into the constant instead: 2x is exact
+// and 2*log2e is log2e with its exponent bumped (0x3fb8aa3b -> 0x4038aa3b),
+// so both forms round the same real product — bit-identical, one VALU slot
+// less per value (tests/test_tanh_fold.py).
+#define TWO_LOG2E 0x1.715476p+1f  // bits 0x4038aa3b
 __device__ inline float fast_tanh(float x) {
-  float e = __expf(2.0f * x);
+  float e = __builtin_amdgcn_exp2f(x * TWO_LOG2E);
   // v_rcp_f32 (1 inst, ~1 ulp) — plain division emits the full IEEE
   // v_div_scale/v_div_fmas chain (~10 insts), which dominated VALUBusy.
   return 1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f);
 }
 
-// 4-wide tanh over one MFMA accumulator: the non-transcendental chain is
-// expressed as f32x4 vector ops so the compiler forms packed v_pk_add /
-// v_pk_fma pairs (2 lanes per issue slot) — only the quarter-rate
-// v_exp/v_rcp stay scalar.  At 96% VALU issue saturation (v7 PMC) every
-// saved issue slot is wall time.
-__device__ inline f32x4 fast_tanh4(f32x4 x) {
-  f32x4 x2 = x + x;
-  f32x4 e;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) e[i] = __expf(x2[i]);
-  f32x4 ep1 = e + 1.0f;
-  f32x4 r;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) r[i] = __builtin_amdgcn_rcpf(ep1[i]);
-  return -2.0f * r + 1.0f;
+// 4-wide tanh(acc + bias) over one MFMA accumulator.  Only the
+// quarter-rate v_exp/v_rcp are per-value; the rest of the chain — bias
+// add, scale, +1, -2r+1 — is written on explicit 2-wide halves so that
+// each link is one packed instruction per pair (v_pk_add / v_pk_mul /
+// v_pk_fma: 8 plain VALU slots per call).  Left to the SLP vectoriser as
+// f32x4 or scalar code the shape is fickle: folding the doubling into
+// the constant un-packed the bias add in exchange (profiles/
+// r04_rollout_issue_slots.md).
+__device__ inline f32x2 tanh2_bias(f32x2 acc, f32x2 bias) {
+  const f32x2 m = (acc + bias) * TWO_LOG2E;
+  f32x2 e;
+  e.x = __builtin_amdgcn_exp2f(m.x);
+  e.y = __builtin_amdgcn_exp2f(m.y);
+  const f32x2 ep1 = e + 1.0f;
+  f32x2 r;
+  r.x = __builtin_amdgcn_rcpf(ep1.x);
+  r.y = __builtin_amdgcn_rcpf(ep1.y);
+  return __builtin_elementwise_fma(r, (f32x2){-2.0f, -2.0f},
+                                   (f32x2){1.0f, 1.0f});
+}
+
+__device__ inline f32x4 fast_tanh4_bias(f32x4 acc, f32x4 bias) {
+  const f32x2 lo = tanh2_bias(acc.lo, bias.lo);
+  const f32x2 hi = tanh2_bias(acc.hi, bias.hi);
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
 }
 
 #define FAM_TAG_NOISE 0x45530001u
@@ -86,9 +104,9 @@ __device__ inline f32x4 fast_tanh4(f32x4 x) {
 #define NPARAMS (OFF_B3 + ACT)              // 4610
 
 // Layer-1 operands only carry 8 k-slots (obs 4 + 4 zeros): the MFMA is
-// K=32, but the kgrp>0 lane groups feed constant-zero fragments instead
-// of reading LDS zeros — identical math, and the w1/xb tiles shrink from
-// 5 KB to 1 KB each.  That drops the block from ~34 KB to ~25 KB of LDS:
+// K=32, but the kgrp>0 lane groups feed all-zero fragments (one shared
+// 16-byte LDS slot) instead of reading zero-padded tiles — identical
+// math, and the w1/xb tiles shrink from 5 KB to 1 KB each.  That drops the block from ~34 KB to ~25 KB of LDS:
 // 6 workgroups/CU instead of 4 on a VALU-latency-bound kernel.
 #define S1 8   // LDS stride (bf16) for layer-1 operands (16 B rows)
 #define S2 72  // LDS stride (bf16) for K=64 operands
@@ -99,49 +117,72 @@ __device__ inline f32x4 fast_tanh4(f32x4 x) {
 // so the output is ready as the next layer's B-operand.
 //
 // NARROW=true: the operands carry only 8 real k-slots (obs 4 + 4 zero
-// pad); the K=32 MFMA's kgrp>0 lane groups use constant-zero fragments —
+// pad); the K=32 MFMA's kgrp>0 lane groups get all-zero fragments —
 // bit-identical result, 1/4 the fragment LDS traffic, 1/4 the tile LDS.
-template <int K, int AS, int BS, int OS, bool NARROW = false>
-__device__ inline void mfma_strip_tanh(const __hip_bfloat16* __restrict__ A,
-                                       const __hip_bfloat16* __restrict__ B,
-                                       const float* __restrict__ bias,
-                                       __hip_bfloat16* __restrict__ out,
-                                       int wave, int lane) {
-  const int r0 = wave * 16;
-  const int arow = r0 + (lane & 15);
-  const int kgrp = lane >> 4;  // 0..3
-  const bf16x8 zfrag = {};
+// Those lanes read the zeros from `zero16`, one shared 16-byte slot of
+// LDS zeros, through the same unconditional ds_read_b128 as the kgrp==0
+// lanes read their row (a broadcast read): selecting the ADDRESS instead
+// of the value needs no v_mov zeroing and no exec-mask toggling around
+// the load, and the addresses are loop-invariant where the caller loops.
+template <int S, bool NARROW>
+__device__ inline const bf16x8* strip_frag_ptr(
+    const __hip_bfloat16* __restrict__ M, const __hip_bfloat16* zero16,
+    int row, int kk, int kgrp) {
+  if (NARROW)
+    return reinterpret_cast<const bf16x8*>(kgrp == 0 ? &M[row * S] : zero16);
+  return reinterpret_cast<const bf16x8*>(&M[row * S + kk * 32 + kgrp * 8]);
+}
 
-  bf16x8 afrag[K / 32];
+// This lane's A fragments for its wave's 16-row strip, and its 4 bias
+// values (rows drow..drow+3, drow = wave*16 + kgrp*4).  Both depend only
+// on the policy, so a caller that loops over steps loads them once.
+template <int K, int AS, bool NARROW = false>
+__device__ inline void strip_load_a(const __hip_bfloat16* __restrict__ A,
+                                    const __hip_bfloat16* zero16, int wave,
+                                    int lane, bf16x8 (&afrag)[K / 32]) {
+#pragma unroll
+  for (int kk = 0; kk < K / 32; ++kk)
+    afrag[kk] = *strip_frag_ptr<AS, NARROW>(A, zero16,
+                                            wave * 16 + (lane & 15), kk,
+                                            lane >> 4);
+}
+
+__device__ inline f32x4 strip_load_bias(const float* __restrict__ bias,
+                                        int wave, int lane) {
+  return *reinterpret_cast<const f32x4*>(
+      &bias[wave * 16 + (lane >> 4) * 4]);
+}
+
+// acc for column tile ct of the strip (afrag from strip_load_a).
+template <int K, int BS, bool NARROW>
+__device__ inline f32x4 strip_mfma(const bf16x8 (&afrag)[K / 32],
+                                   const __hip_bfloat16* __restrict__ B,
+                                   const __hip_bfloat16* zero16, int ct,
+                                   int lane) {
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int kk = 0; kk < K / 32; ++kk) {
-    afrag[kk] = (NARROW && kgrp != 0)
-                    ? zfrag
-                    : *reinterpret_cast<const bf16x8*>(
-                          &A[arow * AS + (NARROW ? 0 : kk * 32 + kgrp * 8)]);
+    const bf16x8 bfrag = *strip_frag_ptr<BS, NARROW>(
+        B, zero16, ct * 16 + (lane & 15), kk, lane >> 4);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag[kk], bfrag, acc, 0,
+                                                  0, 0);
   }
+  return acc;
+}
 
+template <int K, int BS, int OS, bool NARROW = false>
+__device__ inline void mfma_strip_tanh_pre(
+    const bf16x8 (&afrag)[K / 32], const __hip_bfloat16* __restrict__ B,
+    const __hip_bfloat16* zero16, f32x4 biasq,
+    __hip_bfloat16* __restrict__ out, int wave, int lane) {
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct) {
     const int bcol = ct * 16 + (lane & 15);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kk = 0; kk < K / 32; ++kk) {
-      bf16x8 bfrag =
-          (NARROW && kgrp != 0)
-              ? zfrag
-              : *reinterpret_cast<const bf16x8*>(
-                    &B[bcol * BS + (NARROW ? 0 : kk * 32 + kgrp * 8)]);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag[kk], bfrag, acc,
-                                                    0, 0, 0);
-    }
+    const f32x4 acc = strip_mfma<K, BS, NARROW>(afrag, B, zero16, ct, lane);
     // D: row = r0 + kgrp*4 + ri, col = bcol.  The 4 rows are consecutive:
     // pack one 8-byte store into out[col][row..row+3].
-    const int drow = r0 + kgrp * 4;
-    f32x4 zb;
-#pragma unroll
-    for (int ri = 0; ri < 4; ++ri) zb[ri] = acc[ri] + bias[drow + ri];
-    const f32x4 th = fast_tanh4(zb);
+    const int drow = wave * 16 + (lane >> 4) * 4;
+    const f32x4 th = fast_tanh4_bias(acc, biasq);
     union {
       __hip_bfloat16 h[4];
       unsigned long long u;
@@ -152,6 +193,21 @@ __device__ inline void mfma_strip_tanh(const __hip_bfloat16* __restrict__ A,
   }
 }
 
+// One-shot form (standalone forward / probe kernels): loads the A
+// fragments and bias itself.  zero16 is only read when NARROW.
+template <int K, int AS, int BS, int OS, bool NARROW = false>
+__device__ inline void mfma_strip_tanh(const __hip_bfloat16* __restrict__ A,
+                                       const __hip_bfloat16* __restrict__ B,
+                                       const float* __restrict__ bias,
+                                       __hip_bfloat16* __restrict__ out,
+                                       int wave, int lane,
+                                       const __hip_bfloat16* zero16 = nullptr) {
+  bf16x8 afrag[K / 32];
+  strip_load_a<K, AS, NARROW>(A, zero16, wave, lane, afrag);
+  mfma_strip_tanh_pre<K, BS, OS, NARROW>(
+      afrag, B, zero16, strip_load_bias(bias, wave, lane), out, wave, lane);
+}
+
 // Layer-2 strip with the logits fused into the MFMA epilogue: the
 // activations stay in fp32 registers (no bf16 pack / LDS store — they
 // feed nothing but the logits), each lane accumulates its 4 rows'
@@ -159,53 +215,33 @@ __device__ inline void mfma_strip_tanh(const __hip_bfloat16* __restrict__ A,
 // the 4 kgrp lane groups yields the wave's per-env partial, written to
 // lpart[wave][env].  Removes the old D1 phase, its barrier, and all h2
 // LDS traffic.  w3r = this lane's 8 w3 weights (2 actions x 4 rows).
-template <int K, int AS, int BS>
+//
+// The reduce stays per column tile on purpose: its permutes overlap the
+// next tile's MFMA and tanh chain.  Batching all four tiles' permutes
+// behind two waits measured 4.8% SLOWER (profiles/
+// r04_rollout_issue_slots.md).
+template <int K, int BS>
 __device__ inline void mfma_strip_logits(
-    const __hip_bfloat16* __restrict__ A,
-    const __hip_bfloat16* __restrict__ B, const float* __restrict__ bias,
-    const float* __restrict__ w3r, float (*lpart)[ENVS][2], int wave,
-    int lane) {
-  const int r0 = wave * 16;
-  const int arow = r0 + (lane & 15);
-  const int kgrp = lane >> 4;
-
-  bf16x8 afrag[K / 32];
-#pragma unroll
-  for (int kk = 0; kk < K / 32; ++kk) {
-    afrag[kk] = *reinterpret_cast<const bf16x8*>(
-        &A[arow * AS + kk * 32 + kgrp * 8]);
-  }
-
+    const bf16x8 (&afrag)[K / 32], const __hip_bfloat16* __restrict__ B,
+    f32x4 biasq, const float* __restrict__ w3r, float (*lpart)[ENVS][2],
+    int wave, int lane) {
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct) {
-    const int bcol = ct * 16 + (lane & 15);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kk = 0; kk < K / 32; ++kk) {
-      bf16x8 bfrag = *reinterpret_cast<const bf16x8*>(
-          &B[bcol * BS + kk * 32 + kgrp * 8]);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag[kk], bfrag, acc,
-                                                    0, 0, 0);
-    }
-    const int drow = r0 + kgrp * 4;
-    f32x4 zb;
-#pragma unroll
-    for (int ri = 0; ri < 4; ++ri) zb[ri] = acc[ri] + bias[drow + ri];
-    const f32x4 h = fast_tanh4(zb);
+    const f32x4 acc = strip_mfma<K, BS, false>(afrag, B, nullptr, ct, lane);
+    const f32x4 h = fast_tanh4_bias(acc, biasq);
     float p0 = 0.f, p1 = 0.f;
 #pragma unroll
     for (int ri = 0; ri < 4; ++ri) {
       p0 += w3r[ri] * h[ri];
       p1 += w3r[4 + ri] * h[ri];
     }
-    // reduce over the 4 kgrp groups (lanes l, l^16, l^32 share bcol)
     p0 += __shfl_xor(p0, 16, 64);
     p1 += __shfl_xor(p1, 16, 64);
     p0 += __shfl_xor(p0, 32, 64);
     p1 += __shfl_xor(p1, 32, 64);
-    if (kgrp == 0) {
-      lpart[wave][bcol][0] = p0;
-      lpart[wave][bcol][1] = p1;
+    if ((lane >> 4) == 0) {
+      lpart[wave][ct * 16 + lane][0] = p0;
+      lpart[wave][ct * 16 + lane][1] = p1;
     }
   }
 }
@@ -215,8 +251,8 @@ struct PolicyLds {
   alignas(16) __hip_bfloat16 w1[HID][S1];
   alignas(16) __hip_bfloat16 w2[HID][S2];
   alignas(16) __hip_bfloat16 w3[ACT][HID];
-  float b1[HID];
-  float b2[HID];
+  alignas(16) float b1[HID];  // read as f32x4 quads (strip_load_bias)
+  alignas(16) float b2[HID];
   float b3[ACT];
 };
 
@@ -245,6 +281,7 @@ struct RolloutLds {
   // registers), so only the layer-1 B operand lives here (~35 KB block
   // => 4 workgroups/CU).
   alignas(16) __hip_bfloat16 xb[ENVS][S1];
+  alignas(16) __hip_bfloat16 zero16[8];     // layer-1 kgrp>0 fragments
   alignas(16) __hip_bfloat16 h1[ENVS][S2];  // B-operand layer 2
   float S[2][ENVS][OBS];      // env state (double-buffered)
   float lpart[4][ENVS][2];  // per-wave logits partials (C -> D2)
@@ -260,7 +297,8 @@ struct RolloutLds {
 // ---------------------------------------------------------------------------
 
 // Everything in RolloutLds except the policy values: zero the K-padding of
-// W1 (A-side zeros make pad products zero) and of xb, draw the env init
+// W1 (A-side zeros make pad products zero) and of xb, the shared zero
+// fragment slot, draw the env init
 // state (member-independent: common random numbers from seed, iter), zero
 // the stat accumulators.  The caller fills L.pol and then barriers.
 template <bool STATS>
@@ -275,6 +313,7 @@ __device__ __forceinline__ void rollout_init_lds(RolloutLds& L, int tid,
     L.xb[idx / (S1 - OBS)][OBS + idx % (S1 - OBS)] =
         __float2bfloat16(0.f);
   }
+  if (tid < 8) L.zero16[tid] = __float2bfloat16(0.f);
   if (tid < ENVS) {
     float z[4];
     fam_normal4(seed, iter, (uint32_t)tid, 0u, FAM_TAG_ENV, 0u, z);
@@ -330,6 +369,16 @@ __device__ __forceinline__ float rollout_steps(
     }
   }
 
+  // Loop-invariant MFMA operands, loaded once for the whole horizon: both
+  // layers' A fragments (W1: 4 VGPRs, W2: 8) and bias quads (4 + 4).  The
+  // kernels must stay at <= 80 VGPRs (6 waves/SIMD) with these resident
+  // (72 today).
+  bf16x8 a1[KPAD / 32], a2[HID / 32];
+  strip_load_a<KPAD, S1, true>(&L.pol.w1[0][0], L.zero16, wave, lane, a1);
+  strip_load_a<HID, S2>(&L.pol.w2[0][0], nullptr, wave, lane, a2);
+  const f32x4 b1q = strip_load_bias(L.pol.b1, wave, lane);
+  const f32x4 b2q = strip_load_bias(L.pol.b2, wave, lane);
+
   // prologue "phase A" for t=0: stats + normalized obs from the init state
   {
     const float s = L.S[0][env][dd];
@@ -345,13 +394,12 @@ __device__ __forceinline__ float rollout_steps(
     const int cur = t & 1;
     __syncthreads();
     // ---- phase B: h1 = tanh(W1 x + b1)  (MFMA, K=32) ------------------
-    mfma_strip_tanh<KPAD, S1, S1, S2, true>(&L.pol.w1[0][0], &L.xb[0][0],
-                                            L.pol.b1, &L.h1[0][0], wave,
-                                            lane);
+    mfma_strip_tanh_pre<KPAD, S1, S2, true>(a1, &L.xb[0][0], L.zero16, b1q,
+                                            &L.h1[0][0], wave, lane);
     __syncthreads();
     // ---- phase C: h2 stays in registers; logits fused (MFMA, K=64) ----
-    mfma_strip_logits<HID, S2, S2>(&L.pol.w2[0][0], &L.h1[0][0],
-                                   L.pol.b2, w3r, L.lpart, wave, lane);
+    mfma_strip_logits<HID, S2>(a2, &L.h1[0][0], b2q, w3r, L.lpart, wave,
+                               lane);
     __syncthreads();
     // ---- phase D2 (+A of t+1): action, env step, stats, next xb -------
     {
@@ -638,6 +686,7 @@ mlp_policy_forward(const float* __restrict__ theta,
                    float* __restrict__ logits) {
   __shared__ PolicyLds pol;
   __shared__ alignas(16) __hip_bfloat16 xb[ENVS][S1];
+  __shared__ alignas(16) __hip_bfloat16 zero16[8];
   __shared__ alignas(16) __hip_bfloat16 h1[ENVS][S2];
   __shared__ alignas(16) __hip_bfloat16 h2[ENVS][S2];
   const int tid = threadIdx.x;
@@ -654,9 +703,10 @@ mlp_policy_forward(const float* __restrict__ theta,
     float v = (d < OBS && row0 + e < batch) ? X[(row0 + e) * OBS + d] : 0.f;
     xb[e][d] = __float2bfloat16(v);
   }
+  if (tid < 8) zero16[tid] = __float2bfloat16(0.f);
   __syncthreads();
   mfma_strip_tanh<KPAD, S1, S1, S2, true>(&pol.w1[0][0], &xb[0][0], pol.b1,
-                                          &h1[0][0], wave, lane);
+                                          &h1[0][0], wave, lane, zero16);
   __syncthreads();
   mfma_strip_tanh<HID, S2, S2, S2>(&pol.w2[0][0], &h1[0][0], pol.b2,
                                    &h2[0][0], wave, lane);
@@ -687,7 +737,7 @@ mfma_gemm64_probe(const float* __restrict__ A64,
   __shared__ alignas(16) __hip_bfloat16 a[HID][S2];
   __shared__ alignas(16) __hip_bfloat16 b[HID][S2];   // stored [col][k]
   __shared__ alignas(16) __hip_bfloat16 c[HID][S2];   // written [col][row]
-  __shared__ float zero_bias[HID];
+  __shared__ alignas(16) float zero_bias[HID];
   const int tid = threadIdx.x;
   for (int idx = tid; idx < HID * HID; idx += blockDim.x) {
     int r = idx >> 6, k = idx & 63;
