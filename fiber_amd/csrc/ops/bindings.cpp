@@ -38,6 +38,8 @@ extern "C" __global__ void mlp_policy_forward(const float*, const float*,
                                               int, float*);
 extern "C" __global__ void mfma_gemm64_probe(const float*, const float*,
                                              float*);
+extern "C" __global__ void logits_reduce_probe(const float*, const float*,
+                                               float*, float*);
 // conv policy pipeline (conv_kernels.hip)
 extern "C" __global__ void es_perturb(const float*, int, int, float,
                                       uint32_t, const uint32_t*, int,
@@ -217,6 +219,17 @@ static void launch_gemm64_probe(uintptr_t a, uintptr_t b, uintptr_t c,
   check(hipGetLastError(), "mfma_gemm64_probe launch");
 }
 
+// p0, p1: [4][64] partials; out_shfl, out_swap: [64][2].  One wave.
+static void launch_logits_reduce_probe(uintptr_t p0, uintptr_t p1,
+                                       uintptr_t out_shfl,
+                                       uintptr_t out_swap,
+                                       uintptr_t stream) {
+  hipLaunchKernelGGL(logits_reduce_probe, dim3(1), dim3(64), 0,
+                     (hipStream_t)stream, (const float*)p0,
+                     (const float*)p1, (float*)out_shfl, (float*)out_swap);
+  check(hipGetLastError(), "logits_reduce_probe launch");
+}
+
 // ---- conv pipeline launchers ---------------------------------------------
 
 static void launch_perturb(uintptr_t theta, int nparams, int np_pad,
@@ -352,6 +365,9 @@ PYBIND11_MODULE(_ops, m) {
         py::arg("stream"));
   m.def("mfma_gemm64_probe", &launch_gemm64_probe, py::arg("a"),
         py::arg("b"), py::arg("c"), py::arg("stream"));
+  m.def("logits_reduce_probe", &launch_logits_reduce_probe, py::arg("p0"),
+        py::arg("p1"), py::arg("out_shfl"), py::arg("out_swap"),
+        py::arg("stream"));
 
   m.attr("NP_CONV") = 677686;
   m.attr("NP_CONV_PAD") = 677688;

@@ -106,8 +106,9 @@ __device__ inline f32x4 fast_tanh4_bias(f32x4 acc, f32x4 bias) {
 // Layer-1 operands only carry 8 k-slots (obs 4 + 4 zeros): the MFMA is
 // K=32, but the kgrp>0 lane groups feed all-zero fragments (one shared
 // 16-byte LDS slot) instead of reading zero-padded tiles — identical
-// math, and the w1/xb tiles shrink from 5 KB to 1 KB each.  That drops the block from ~34 KB to ~25 KB of LDS:
-// 6 workgroups/CU instead of 4 on a VALU-latency-bound kernel.
+// math, and the w1/xb tiles shrink from 5 KB to 1 KB each (8 KB less LDS
+// per block).  With h1 sharing the W2 staging tile (RolloutLds) the block
+// is ~16 KB: LDS allows 10 workgroups/CU and no longer caps occupancy.
 #define S1 8   // LDS stride (bf16) for layer-1 operands (16 B rows)
 #define S2 72  // LDS stride (bf16) for K=64 operands
 
@@ -208,41 +209,106 @@ __device__ inline void mfma_strip_tanh(const __hip_bfloat16* __restrict__ A,
       afrag, B, zero16, strip_load_bias(bias, wave, lane), out, wave, lane);
 }
 
+// Cross-kgrp reduce of the logits partials, for the column tiles ct and
+// ct+1 at once.  Each lane holds its 4 rows' contribution to both logits
+// of both tiles (p0 / p1 = logit 0 / 1); the sum over the wave's four
+// 16-lane rows (kgrp 0..3) is one env's partial.  lrow = lpart[wave].
+//
+// Reference form: the shfl_xor tree, (k0+k1) + (k2+k3), through
+// ds_bpermute, with the kgrp==0 lanes storing under an exec mask.  Only
+// logits_reduce_probe uses it; the step loop runs the swap form below.
+__device__ inline void logits_reduce_shfl(float p0, float p1,
+                                          float (*lrow)[2], int ct,
+                                          int lane) {
+  p0 += __shfl_xor(p0, 16, 64);
+  p1 += __shfl_xor(p1, 16, 64);
+  p0 += __shfl_xor(p0, 32, 64);
+  p1 += __shfl_xor(p1, 32, 64);
+  if ((lane >> 4) == 0) {
+    lrow[ct * 16 + lane][0] = p0;
+    lrow[ct * 16 + lane][1] = p1;
+  }
+}
+
+// Swap form: the same tree in the VALU.  Writing a register's four
+// 16-lane rows as [r0 r1 r2 r3]:
+//   v_permlane16_swap(x, y): x = [x0 y0 x2 y2], y = [x1 y1 x3 y3]
+//   v_permlane32_swap(x, y): x = [x0 x1 y0 y1], y = [x2 x3 y2 y3]
+// With p0 = [a0 a1 a2 a3], p1 = [b0 b1 b2 b3] of tile ct, one 16-swap and
+// an add give s = [a0+a1, b0+b1, a2+a3, b2+b3]; tile ct+1 likewise gives
+// t = [c0+c1, ...].  One 32-swap of (s, t) and an add give
+// [a, b, c, d]: row kgrp holds logit kgrp&1 of tile ct + (kgrp>>1), each
+// the sum (k0+k1) + (k2+k3) of the very operands the shfl tree adds —
+// identical bits (tests/gpu/test_logits_reduce.py).  3 swaps + 3 adds per
+// tile pair against 8 bpermutes + 8 adds, no LDS round trip to wait for,
+// and the store is one unmasked full-wave ds_write.
+__device__ inline f32x2 permlane16_swap(float x, float y) {
+  const auto r = __builtin_amdgcn_permlane16_swap(
+      __float_as_uint(x), __float_as_uint(y), false, false);
+  return (f32x2){__uint_as_float(r[0]), __uint_as_float(r[1])};
+}
+
+__device__ inline f32x2 permlane32_swap(float x, float y) {
+  const auto r = __builtin_amdgcn_permlane32_swap(
+      __float_as_uint(x), __float_as_uint(y), false, false);
+  return (f32x2){__uint_as_float(r[0]), __uint_as_float(r[1])};
+}
+
+__device__ inline void logits_reduce_swap(float p0a, float p1a, float p0b,
+                                          float p1b, float (*lrow)[2],
+                                          int ct, int lane) {
+  const f32x2 sa = permlane16_swap(p0a, p1a);
+  const f32x2 sb = permlane16_swap(p0b, p1b);
+  const f32x2 s = permlane32_swap(sa.x + sa.y, sb.x + sb.y);
+  const int kgrp = lane >> 4;
+  lrow[(ct + (kgrp >> 1)) * 16 + (lane & 15)][kgrp & 1] = s.x + s.y;
+}
+
 // Layer-2 strip with the logits fused into the MFMA epilogue: the
 // activations stay in fp32 registers (no bf16 pack / LDS store — they
 // feed nothing but the logits), each lane accumulates its 4 rows'
-// contribution to both action logits, and a 2-stage shfl_xor reduce over
-// the 4 kgrp lane groups yields the wave's per-env partial, written to
-// lpart[wave][env].  Removes the old D1 phase, its barrier, and all h2
-// LDS traffic.  w3r = this lane's 8 w3 weights (2 actions x 4 rows).
+// contribution to both action logits, and the reduce over the 4 kgrp lane
+// groups yields the wave's per-env partial, written to lpart[wave][env].
+// Removes the old D1 phase, its barrier, and all h2 LDS traffic.  w3p =
+// this lane's 8 w3 weights: for each of its 4 rows the pair (action 0,
+// action 1).
 //
-// The reduce stays per column tile on purpose: its permutes overlap the
-// next tile's MFMA and tanh chain.  Batching all four tiles' permutes
-// behind two waits measured 4.8% SLOWER (profiles/
-// r04_rollout_issue_slots.md).
+// The reduce runs on tile pairs (0,1) and (2,3) in the VALU
+// (logits_reduce_swap): the first pair's swaps sit between the second
+// pair's MFMAs and tanh chains, and no wave waits on LDS for a lane
+// exchange.  The earlier ds_bpermute form had to stay per tile for that
+// overlap — batching its permutes behind two waits measured 4.8% slower
+// (profiles/r04_rollout_issue_slots.md); the swap form against it is in
+// profiles/r05_rollout_occupancy.md.
 template <int K, int BS>
 __device__ inline void mfma_strip_logits(
     const bf16x8 (&afrag)[K / 32], const __hip_bfloat16* __restrict__ B,
-    f32x4 biasq, const float* __restrict__ w3r, float (*lpart)[ENVS][2],
-    int wave, int lane) {
+    f32x4 biasq, const f32x2 (&w3p)[4], float (*lpart)[ENVS][2], int wave,
+    int lane) {
 #pragma unroll
-  for (int ct = 0; ct < 4; ++ct) {
-    const f32x4 acc = strip_mfma<K, BS, false>(afrag, B, nullptr, ct, lane);
-    const f32x4 h = fast_tanh4_bias(acc, biasq);
-    float p0 = 0.f, p1 = 0.f;
+  for (int cp = 0; cp < 4; cp += 2) {
+    f32x2 p[2];  // {p0, p1} of tiles cp, cp+1
 #pragma unroll
-    for (int ri = 0; ri < 4; ++ri) {
-      p0 += w3r[ri] * h[ri];
-      p1 += w3r[4 + ri] * h[ri];
+    for (int c = 0; c < 2; ++c) {
+      const f32x4 acc =
+          strip_mfma<K, BS, false>(afrag, B, nullptr, cp + c, lane);
+      const f32x4 h = fast_tanh4_bias(acc, biasq);
+      // Two scalar fma chains, 8 slots per tile.  While p0 / p1 fed
+      // adjacent stores the compiler packed them (4 v_pk_fma); feeding the
+      // swaps it does not.  Spelling the pair out as f32x2 fmas packs them
+      // again but costs 6-9 VGPRs (below 7 waves/SIMD, or scratch) and
+      // that build did not reproduce its own results across launch
+      // shapes (profiles/r05_rollout_occupancy.md): keep the scalar form.
+      float p0 = 0.f, p1 = 0.f;
+#pragma unroll
+      for (int ri = 0; ri < 4; ++ri) {
+        p0 += w3p[ri].x * h[ri];
+        p1 += w3p[ri].y * h[ri];
+      }
+      p[c] = (f32x2){p0, p1};
     }
-    p0 += __shfl_xor(p0, 16, 64);
-    p1 += __shfl_xor(p1, 16, 64);
-    p0 += __shfl_xor(p0, 32, 64);
-    p1 += __shfl_xor(p1, 32, 64);
-    if ((lane >> 4) == 0) {
-      lpart[wave][ct * 16 + lane][0] = p0;
-      lpart[wave][ct * 16 + lane][1] = p1;
-    }
+    logits_reduce_swap(p[0].x, p[0].y, p[1].x, p[1].y, lpart[wave], cp,
+                       lane);
   }
 }
 
@@ -278,15 +344,24 @@ __device__ inline void store_param(PolicyLds* p, int j, float v) {
 struct RolloutLds {
   PolicyLds pol;
   // layer-2 output never touches LDS (fused-logits epilogue keeps it in
-  // registers), so only the layer-1 B operand lives here (~35 KB block
-  // => 4 workgroups/CU).
+  // registers), so only the layer-1 B operand and the layer-2 B operand
+  // h1 live here — and h1 has no tile of its own, see h1() below.
+  // 16,208 B per block: LDS allows 10 workgroups/CU, so the VGPR count
+  // alone sets the occupancy.
   alignas(16) __hip_bfloat16 xb[ENVS][S1];
   alignas(16) __hip_bfloat16 zero16[8];     // layer-1 kgrp>0 fragments
-  alignas(16) __hip_bfloat16 h1[ENVS][S2];  // B-operand layer 2
   float S[2][ENVS][OBS];      // env state (double-buffered)
   float lpart[4][ENVS][2];  // per-wave logits partials (C -> D2)
   float ostat[2 * OBS + 1];   // sum, sumsq, count
+
+  // B-operand of layer 2, [ENVS][S2].  It shares pol.w2 ([HID][S2], the
+  // same shape: ENVS == HID): W2 is only staged there until rollout_steps
+  // has pulled its A fragments into registers, which is before the step
+  // loop; h1 is first written inside it.  This accessor is the one place
+  // that knows; the invariant is spelled out where rollout_steps loads a2.
+  __device__ __hip_bfloat16* h1() { return &pol.w2[0][0]; }
 };
+static_assert(ENVS == HID, "h1 [ENVS][S2] shares the W2 tile [HID][S2]");
 
 // ---------------------------------------------------------------------------
 // Pieces shared by es_rollout_mlp (perturbed members, obs statistics) and
@@ -359,20 +434,27 @@ __device__ __forceinline__ float rollout_steps(
   const float one_if_d0 = (dd == 0) ? 1.f : 0.f;
   // this lane's w3 slice for the fused logits epilogue: rows
   // drow..drow+3 of both actions (drow = wave*16 + kgrp*4)
-  float w3r[2 * 4];
+  f32x2 w3p[4];
   {
     const int drow = wave * 16 + (lane >> 4) * 4;
 #pragma unroll
     for (int ri = 0; ri < 4; ++ri) {
-      w3r[ri] = __bfloat162float(L.pol.w3[0][drow + ri]);
-      w3r[4 + ri] = __bfloat162float(L.pol.w3[1][drow + ri]);
+      w3p[ri].x = __bfloat162float(L.pol.w3[0][drow + ri]);
+      w3p[ri].y = __bfloat162float(L.pol.w3[1][drow + ri]);
     }
   }
 
   // Loop-invariant MFMA operands, loaded once for the whole horizon: both
-  // layers' A fragments (W1: 4 VGPRs, W2: 8) and bias quads (4 + 4).  The
-  // kernels must stay at <= 80 VGPRs (6 waves/SIMD) with these resident
-  // (72 today).
+  // layers' A fragments (W1: 4 VGPRs, W2: 8) and bias quads (4 + 4).  LDS
+  // no longer limits residency, so the VGPR count decides it: the kernels
+  // must stay at <= 72 VGPRs (7 waves/SIMD) with these resident, and
+  // without scratch.
+  //
+  // L.h1() is L.pol.w2.  That is sound because nothing reads W2 from LDS
+  // after the a2 load below: every wave issues it here, the loop-top
+  // __syncthreads() waits for the wave's outstanding LDS reads before it
+  // arrives at the barrier, and the first h1 write of any wave (phase B)
+  // comes after that barrier.  Do not read L.pol.w2 past this point.
   bf16x8 a1[KPAD / 32], a2[HID / 32];
   strip_load_a<KPAD, S1, true>(&L.pol.w1[0][0], L.zero16, wave, lane, a1);
   strip_load_a<HID, S2>(&L.pol.w2[0][0], nullptr, wave, lane, a2);
@@ -395,11 +477,10 @@ __device__ __forceinline__ float rollout_steps(
     __syncthreads();
     // ---- phase B: h1 = tanh(W1 x + b1)  (MFMA, K=32) ------------------
     mfma_strip_tanh_pre<KPAD, S1, S2, true>(a1, &L.xb[0][0], L.zero16, b1q,
-                                            &L.h1[0][0], wave, lane);
+                                            L.h1(), wave, lane);
     __syncthreads();
     // ---- phase C: h2 stays in registers; logits fused (MFMA, K=64) ----
-    mfma_strip_logits<HID, S2>(a2, &L.h1[0][0], b2q, w3r, L.lpart, wave,
-                               lane);
+    mfma_strip_logits<HID, S2>(a2, L.h1(), b2q, w3p, L.lpart, wave, lane);
     __syncthreads();
     // ---- phase D2 (+A of t+1): action, env step, stats, next xb -------
     {
@@ -410,9 +491,13 @@ __device__ __forceinline__ float rollout_steps(
                        L.lpart[1][env][1] + L.lpart[2][env][1] +
                        L.lpart[3][env][1];
       const float asign = (l1 > l0) ? 1.f : -1.f;
+      // One fma per term, spelled out: left as `drive += a * s` the
+      // compiler contracts all four or, with a different schedule around
+      // it, multiplies two of them separately — other bits.
       float drive = 0.f;
 #pragma unroll
-      for (int e = 0; e < OBS; ++e) drive += eA_d[e] * L.S[cur][env][e];
+      for (int e = 0; e < OBS; ++e)
+        drive = fmaf(eA_d[e], L.S[cur][env][e], drive);
       // a*b + c*d leaves the compiler free to fuse either product into
       // the add, and the two choices round differently.  The fma is
       // spelled out (0.97*s rounded, 0.08*tanh fused) so that every
@@ -453,7 +538,15 @@ __device__ __forceinline__ float reward_reduce_wave0(
   return r;
 }
 
-extern "C" __global__ void __launch_bounds__(256)
+// Waves per SIMD the two rollout kernels are compiled for (the second
+// __launch_bounds__ argument: the register allocator and the scheduler
+// then hold the kernel to 512 / ROLLOUT_WAVES VGPRs instead of trading a
+// resident wave for a longer schedule).  LDS allows 10 blocks per CU.
+#ifndef ROLLOUT_WAVES
+#define ROLLOUT_WAVES 7
+#endif
+
+extern "C" __global__ void __launch_bounds__(256, ROLLOUT_WAVES)
 es_rollout_mlp(const float* __restrict__ theta, float sigma, uint32_t seed,
                uint32_t iter, int horizon, int member_offset,
                const float* __restrict__ obs_mu,
@@ -528,7 +621,7 @@ es_rollout_mlp(const float* __restrict__ theta, float sigma, uint32_t seed,
 // step loop are es_rollout_mlp's (common random numbers from seed,
 // iter), so scores[k][m] is bit-identical to that kernel's fitness for
 // theta_k at sigma = 0.  No obs statistics, no atomics.
-extern "C" __global__ void __launch_bounds__(256)
+extern "C" __global__ void __launch_bounds__(256, ROLLOUT_WAVES)
 es_eval_matrix(const float* __restrict__ thetas,  // [K][NPARAMS]
                const float* __restrict__ obs_mu,  // [K][OBS]
                const float* __restrict__ obs_nu,  // [K][OBS]
@@ -755,5 +848,41 @@ mfma_gemm64_probe(const float* __restrict__ A64,
   for (int idx = tid; idx < HID * HID; idx += blockDim.x) {
     int col = idx >> 6, row = idx & 63;
     C64T[col * HID + row] = __bfloat162float(c[col][row]);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Logits-reduce probe: one wave takes per-lane partials p0[4][64] and
+// p1[4][64] (4 column tiles x 64 lanes) through both forms of the
+// cross-kgrp reduce and returns the lpart row each one writes, [ENVS][2].
+// The rollout outputs see the logits only through l1 > l0; this compares
+// the raw bits of the swap form (what the step loop runs) with the shfl
+// tree it replaced.
+// ---------------------------------------------------------------------------
+extern "C" __global__ void __launch_bounds__(64)
+logits_reduce_probe(const float* __restrict__ p0,  // [4][64]
+                    const float* __restrict__ p1,  // [4][64]
+                    float* __restrict__ out_shfl,  // [ENVS][2]
+                    float* __restrict__ out_swap)  // [ENVS][2]
+{
+  __shared__ float lrow[2][ENVS][2];
+  const int lane = threadIdx.x;
+  float a[4], b[4];
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) {
+    a[ct] = p0[ct * 64 + lane];
+    b[ct] = p1[ct * 64 + lane];
+  }
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct)
+    logits_reduce_shfl(a[ct], b[ct], lrow[0], ct, lane);
+#pragma unroll
+  for (int cp = 0; cp < 4; cp += 2)
+    logits_reduce_swap(a[cp], b[cp], a[cp + 1], b[cp + 1], lrow[1], cp, lane);
+  __syncthreads();
+#pragma unroll
+  for (int a01 = 0; a01 < 2; ++a01) {
+    out_shfl[lane * 2 + a01] = lrow[0][lane][a01];
+    out_swap[lane * 2 + a01] = lrow[1][lane][a01];
   }
 }

@@ -234,5 +234,28 @@ def mfma_gemm64_probe(a, b):
     return out_t.T.contiguous()
 
 
+def logits_reduce_probe(p0, p1):
+    """The rollout loop's cross-lane logits reduce on its own: for per-lane
+    partials ``p0[4][64]``, ``p1[4][64]`` (4 column tiles x 64 lanes)
+    returns ``(shfl, swap)``, the ``[64 env][2 logits]`` partial row as
+    written by the shfl_xor tree and by the permlane-swap form the step
+    loop runs.  The two must agree bit for bit."""
+    ops = _require_ops()
+    for name, t in (("p0", p0), ("p1", p1)):
+        _check(t, name)
+        if tuple(t.shape) != (4, 64):
+            raise ValueError("%s must be [4, 64], got %s"
+                             % (name, tuple(t.shape)))
+    if p1.device != p0.device:
+        raise TypeError("p1 is on %s, p0 on %s" % (p1.device, p0.device))
+    shfl = torch.empty(ENVS_PER_MEMBER, ACT_DIM, dtype=torch.float32,
+                       device=p0.device)
+    swap = torch.empty_like(shfl)
+    with torch.cuda.device(p0.device):
+        ops.logits_reduce_probe(p0.data_ptr(), p1.data_ptr(),
+                                shfl.data_ptr(), swap.data_ptr(), _stream())
+    return shfl, swap
+
+
 def ops_available():
     return _OPS is not None
