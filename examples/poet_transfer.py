@@ -13,6 +13,11 @@ N (policy, environment) pairs, each an ESEngine on its own environment
 
 Prints one line per generation and, at the end, generations per second.
 ``examples/poet_loop.py`` is the CPU-plumbing toy of the same outer loop.
+
+``--batched`` runs the same loop on one ``ESPopulation``: the inner ES
+steps of all pairs are one batched rollout / rank / gradient launch each
+instead of one ``ESEngine.step()`` per pair, with the same results (the
+``gen`` lines are identical).
 """
 
 import os as _os
@@ -29,7 +34,7 @@ import time
 
 import torch
 
-from fiber_amd.es import (ESConfig, ESEngine, apply_transfers,
+from fiber_amd.es import (ESConfig, ESEngine, ESPopulation, apply_transfers,
                           make_env_params, select_transfers,
                           transfer_matrix)
 
@@ -52,6 +57,8 @@ def main(argv=None):
                         help="ES steps per pair per generation")
     parser.add_argument("--seed", type=int, default=1234)
     parser.add_argument("--margin", type=float, default=0.0)
+    parser.add_argument("--batched", action="store_true",
+                        help="advance all pairs together (ESPopulation)")
     args = parser.parse_args(argv)
 
     if not torch.cuda.is_available():
@@ -63,6 +70,8 @@ def main(argv=None):
                    seed=args.seed)
 
     envs = [perturbed_env(base, gen, 0.1) for _ in range(args.pairs)]
+    if args.batched:
+        return run_batched(args, cfg, envs, gen, device)
     engines = []
     for i, env in enumerate(envs):
         # one noise stream and one initial policy per pair
@@ -99,6 +108,42 @@ def main(argv=None):
     dt = time.perf_counter() - t0
     print("%d generations of %d pairs in %.3f s: %.2f generations/s, "
           "%d transfers in all"
+          % (args.generations, args.pairs, dt, args.generations / dt,
+             total_transfers))
+    return total_transfers
+
+
+def run_batched(args, cfg, envs, gen, device):
+    """The loop of main() on an ESPopulation: pair i has seed
+    ``args.seed + i``, as engine i has there."""
+    pop = ESPopulation(cfg, [args.seed + i for i in range(args.pairs)],
+                       envs, device=device)
+    total_transfers = 0
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for g in range(args.generations):
+        for _ in range(args.inner_steps):
+            pop.step()
+        scores = pop.transfer_matrix(args.horizon, args.seed, g)
+        transfers = select_transfers(scores, args.margin)
+        pop.apply_transfers(transfers)
+        total_transfers += len(transfers)
+
+        diag = scores.diagonal().cpu()
+        incumbent = diag.clone()
+        for m, k in transfers:
+            incumbent[m] = float(scores[k, m])
+        solved = int(torch.argmax(incumbent))
+        envs[solved] = perturbed_env(envs[solved], gen, 0.05)
+        pop.set_env(solved, *envs[solved])
+        print("gen %d  transfers=%d  diag_mean=%.4f  best_incumbent=%.4f  "
+              "mutated_env=%d"
+              % (g, len(transfers), float(diag.mean()),
+                 float(incumbent.max()), solved))
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    print("%d generations of %d pairs in %.3f s: %.2f generations/s, "
+          "%d transfers in all (batched)"
           % (args.generations, args.pairs, dt, args.generations / dt,
              total_transfers))
     return total_transfers

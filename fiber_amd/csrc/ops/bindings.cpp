@@ -40,6 +40,17 @@ extern "C" __global__ void mfma_gemm64_probe(const float*, const float*,
                                              float*);
 extern "C" __global__ void logits_reduce_probe(const float*, const float*,
                                                float*, float*);
+// per-pair batched kernels (es_pairs_kernels.hip)
+extern "C" __global__ void es_rollout_mlp_pairs(
+    const float*, float, const uint32_t*, uint32_t, int, int, const float*,
+    const float*, const float*, const float*, float*, float*, float*);
+extern "C" __global__ void obs_stat_reduce_pairs(const float*, int, float*);
+extern "C" __global__ void centered_rank_pairs(const float*, int, float*);
+extern "C" __global__ void es_grad_pairs(const float*, int, int,
+                                         const uint32_t*, uint32_t, int,
+                                         float*);
+extern "C" __global__ void es_grad_reduce_pairs(const float*, int, int,
+                                                float*);
 // conv policy pipeline (conv_kernels.hip)
 extern "C" __global__ void es_perturb(const float*, int, int, float,
                                       uint32_t, const uint32_t*, int,
@@ -155,6 +166,85 @@ static void launch_centered_rank(uintptr_t f, int n, uintptr_t out,
   hipLaunchKernelGGL(centered_rank, dim3(bx), dim3(256), 0,
                      (hipStream_t)stream, (const float*)f, n, (float*)out);
   check(hipGetLastError(), "centered_rank launch");
+}
+
+// ---- per-pair batched launchers ------------------------------------------
+// P pairs per launch.  The pair index is flattened into grid.x for the
+// rollout (P*pop outgrows grid.y) and rides grid.y / grid.z elsewhere, so
+// P stops at 65535 there; the Python wrappers check all of this first.
+#define PAIRS_GRID_MAX 65535
+
+static void check_pairs(const char* what, int P) {
+  if (P > PAIRS_GRID_MAX)
+    throw std::runtime_error(std::string(what) +
+                             ": P exceeds the grid limit");
+}
+
+static void launch_rollout_pairs(uintptr_t thetas, double sigma,
+                                 uintptr_t seeds, uint32_t iter, int horizon,
+                                 int P, int pop, uintptr_t obs_mu,
+                                 uintptr_t obs_nu, uintptr_t env_A,
+                                 uintptr_t env_B, uintptr_t fitness,
+                                 uintptr_t obs_stat_part, uintptr_t obs_stat,
+                                 uintptr_t stream) {
+  if (P <= 0 || pop <= 0) return;
+  check_pairs("es_rollout_mlp_pairs", P);
+  const long long blocks = (long long)P * (long long)pop;
+  if (blocks > 0x7FFFFFFFLL)
+    throw std::runtime_error(
+        "es_rollout_mlp_pairs: P*pop exceeds the grid limit");
+  if (horizon < 1)
+    throw std::runtime_error("es_rollout_mlp_pairs: horizon must be >= 1");
+  hipLaunchKernelGGL(es_rollout_mlp_pairs, dim3((unsigned)blocks), dim3(256),
+                     0, (hipStream_t)stream, (const float*)thetas,
+                     (float)sigma, (const uint32_t*)seeds, iter, horizon,
+                     pop, (const float*)obs_mu, (const float*)obs_nu,
+                     (const float*)env_A, (const float*)env_B,
+                     (float*)fitness, (float*)obs_stat_part,
+                     (float*)obs_stat);
+  check(hipGetLastError(), "es_rollout_mlp_pairs launch");
+  // obs_stat_part is [P][pop][2*OBS]; one block per (stat column, pair)
+  hipLaunchKernelGGL(obs_stat_reduce_pairs, dim3(2 * OBS_HOST, P), dim3(256),
+                     0, (hipStream_t)stream, (const float*)obs_stat_part,
+                     pop, (float*)obs_stat);
+  check(hipGetLastError(), "obs_stat_reduce_pairs launch");
+}
+
+static void launch_centered_rank_pairs(uintptr_t f, int P, int n,
+                                       uintptr_t out, uintptr_t stream) {
+  if (P <= 0 || n <= 0) return;
+  check_pairs("centered_rank_pairs", P);
+  hipLaunchKernelGGL(centered_rank_pairs, dim3((n + 255) / 256, P),
+                     dim3(256), 0, (hipStream_t)stream, (const float*)f, n,
+                     (float*)out);
+  check(hipGetLastError(), "centered_rank_pairs launch");
+}
+
+// The split of launch_grad over [0, npairs) for every pair: the same
+// chunk count and per_chunk, partials summed in chunk order.  grad_part
+// holds P * grad_chunks(npairs, nparams) * nparams floats.
+static void launch_grad_pairs(uintptr_t wpair, int P, int npairs,
+                              uintptr_t seeds, uint32_t iter, int nparams,
+                              uintptr_t grad_part, uintptr_t grad,
+                              uintptr_t stream) {
+  if (P <= 0 || npairs <= 0) return;
+  check_pairs("es_grad_pairs", P);
+  const int jblocks = (nparams + 3) / 4;
+  const int bx = (jblocks + 255) / 256;
+  const int chunks = grad_chunks(npairs, nparams);
+  const int per_chunk = (npairs + chunks - 1) / chunks;
+  hipLaunchKernelGGL(es_grad_pairs, dim3(bx, chunks, P), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)wpair, npairs,
+                     per_chunk, (const uint32_t*)seeds, iter, nparams,
+                     chunks == 1 ? (float*)grad : (float*)grad_part);
+  check(hipGetLastError(), "es_grad_pairs launch");
+  if (chunks > 1) {
+    hipLaunchKernelGGL(es_grad_reduce_pairs, dim3((nparams + 255) / 256, P),
+                       dim3(256), 0, (hipStream_t)stream,
+                       (const float*)grad_part, chunks, nparams,
+                       (float*)grad);
+    check(hipGetLastError(), "es_grad_reduce_pairs launch");
+  }
 }
 
 // Sort-based rank for large populations: pack order-preserving uint keys,
@@ -355,6 +445,18 @@ PYBIND11_MODULE(_ops, m) {
         py::arg("nparams"));
   m.def("centered_rank", &launch_centered_rank, py::arg("f"), py::arg("n"),
         py::arg("out"), py::arg("stream"));
+  m.def("es_rollout_mlp_pairs", &launch_rollout_pairs, py::arg("thetas"),
+        py::arg("sigma"), py::arg("seeds"), py::arg("iter"),
+        py::arg("horizon"), py::arg("P"), py::arg("pop"), py::arg("obs_mu"),
+        py::arg("obs_nu"), py::arg("env_A"), py::arg("env_B"),
+        py::arg("fitness"), py::arg("obs_stat_part"), py::arg("obs_stat"),
+        py::arg("stream"));
+  m.def("centered_rank_pairs", &launch_centered_rank_pairs, py::arg("f"),
+        py::arg("P"), py::arg("n"), py::arg("out"), py::arg("stream"));
+  m.def("es_grad_pairs", &launch_grad_pairs, py::arg("wpair"), py::arg("P"),
+        py::arg("npairs"), py::arg("seeds"), py::arg("iter"),
+        py::arg("nparams"), py::arg("grad_part"), py::arg("grad"),
+        py::arg("stream"));
   m.def("centered_rank_sorted_workspace", &centered_rank_sorted_workspace,
         py::arg("n"));
   m.def("centered_rank_sorted", &launch_centered_rank_sorted, py::arg("f"),

@@ -546,6 +546,16 @@ __device__ __forceinline__ float reward_reduce_wave0(
 #define ROLLOUT_WAVES 7
 #endif
 
+// Everything above is the shared device code of the MLP rollout kernels.
+// es_pairs_kernels.hip includes this file with ES_KERNELS_SHARED_ONLY
+// defined to get exactly that and none of the kernels below: the per-pair
+// kernels are a translation unit of their own, so that the machine code
+// of the two kernels here, 3 and 4 VGPRs under the 72 that 7 waves/SIMD
+// allow, cannot depend on them: one more instantiation of rollout_steps
+// in this module has moved their register allocation before
+// (profiles/eval_matrix.md, profiles/es_population.md).
+#ifndef ES_KERNELS_SHARED_ONLY
+
 extern "C" __global__ void __launch_bounds__(256, ROLLOUT_WAVES)
 es_rollout_mlp(const float* __restrict__ theta, float sigma, uint32_t seed,
                uint32_t iter, int horizon, int member_offset,
@@ -886,3 +896,5 @@ logits_reduce_probe(const float* __restrict__ p0,  // [4][64]
     out_swap[lane * 2 + a01] = lrow[1][lane][a01];
   }
 }
+
+#endif  // ES_KERNELS_SHARED_ONLY

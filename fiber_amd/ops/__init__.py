@@ -257,5 +257,151 @@ def logits_reduce_probe(p0, p1):
     return shfl, swap
 
 
+# ---------------------------------------------------------------------------
+# Per-pair batched ops: P independent (policy, environment) pairs per
+# launch, each with its own theta, normaliser, environment and noise seed.
+# For pair p every op returns the bits of its single-pair counterpart.
+# ---------------------------------------------------------------------------
+
+PAIRS_MAX = 65535           # the pair index rides grid.y / grid.z
+RANK_PAIRS_MAX_N = 16384    # where centered_rank switches to the radix path
+
+
+def pair_seeds(seeds, device):
+    """int32 device tensor [P] carrying the 32-bit patterns of the Python
+    ints ``seeds``, masked with the same ``& 0xFFFFFFFF`` that the scalar
+    ops apply to their ``seed`` argument."""
+    vals = []
+    for s in seeds:
+        v = int(s) & 0xFFFFFFFF
+        vals.append(v - (1 << 32) if v >= (1 << 31) else v)
+    return torch.tensor(vals, dtype=torch.int32).to(device).contiguous()
+
+
+def _check_pairs_on(named, anchor_name, anchor):
+    """dtype / device / contiguity of every (name, tensor, dtype), all on
+    the device of ``anchor``."""
+    for name, t, dtype in named:
+        _check(t, name, dtype=dtype)
+        if t.device != anchor.device:
+            raise TypeError("%s is on %s, %s on %s"
+                            % (name, t.device, anchor_name, anchor.device))
+
+
+def _check_pair_count(P):
+    if P < 1 or P > PAIRS_MAX:
+        raise ValueError("P must be in [1, %d], got %d" % (PAIRS_MAX, P))
+
+
+def es_rollout_mlp_pairs(thetas, sigma, seeds, iteration, horizon, pop,
+                         obs_mu, obs_nu, env_A, env_B):
+    """``pop`` perturbed members for each of P pairs in one launch, one
+    workgroup per (pair, member).
+
+    ``thetas[P][NPARAMS]``, ``seeds`` int32 ``[P]`` (see ``pair_seeds``),
+    ``obs_mu[P][4]``, ``obs_nu[P][4]``, ``env_A[P][4][4]``,
+    ``env_B[P][4]``; ``sigma``, ``iteration`` and ``horizon`` are shared.
+    Returns ``(fitness[P][pop], obs_stat[P][9])``; row p of both is
+    bit-identical to ``es_rollout_mlp(thetas[p], sigma, seed_p, iteration,
+    horizon, 0, pop, obs_mu[p], obs_nu[p], env_A[p], env_B[p])``.
+
+    Every argument is validated before anything is launched: TypeError
+    for dtype, device or contiguity, ValueError for shapes and sizes."""
+    ops = _require_ops()
+    _check_pairs_on(
+        (("thetas", thetas, torch.float32), ("seeds", seeds, torch.int32),
+         ("obs_mu", obs_mu, torch.float32), ("obs_nu", obs_nu, torch.float32),
+         ("env_A", env_A, torch.float32), ("env_B", env_B, torch.float32)),
+        "thetas", thetas)
+    if thetas.dim() != 2 or thetas.shape[1] != NPARAMS:
+        raise ValueError("thetas must be [P, %d], got %s"
+                         % (NPARAMS, tuple(thetas.shape)))
+    P = thetas.shape[0]
+    _check_pair_count(P)
+    for name, t, want in (("seeds", seeds, (P,)),
+                          ("obs_mu", obs_mu, (P, OBS_DIM)),
+                          ("obs_nu", obs_nu, (P, OBS_DIM)),
+                          ("env_A", env_A, (P, OBS_DIM, OBS_DIM)),
+                          ("env_B", env_B, (P, OBS_DIM))):
+        if tuple(t.shape) != want:
+            raise ValueError("%s must be %s, got %s"
+                             % (name, list(want), tuple(t.shape)))
+    pop, horizon = int(pop), int(horizon)
+    if pop < 2 or pop % 2:
+        raise ValueError("pop must be even and >= 2 (antithetic pairs), "
+                         "got %d" % pop)
+    if horizon < 1:
+        raise ValueError("horizon must be >= 1, got %d" % horizon)
+    if P * pop >= 2 ** 31:
+        raise ValueError("P*pop = %d exceeds the launch grid" % (P * pop))
+    device = thetas.device
+    fitness = torch.empty(P, pop, dtype=torch.float32, device=device)
+    obs_stat = torch.zeros(P, 2 * OBS_DIM + 1, dtype=torch.float32,
+                           device=device)
+    with torch.cuda.device(device):
+        part = _partial_buffer(device, P * pop * 2 * OBS_DIM)
+        ops.es_rollout_mlp_pairs(
+            thetas.data_ptr(), float(sigma), seeds.data_ptr(),
+            int(iteration) & 0xFFFFFFFF, horizon, P, pop, obs_mu.data_ptr(),
+            obs_nu.data_ptr(), env_A.data_ptr(), env_B.data_ptr(),
+            fitness.data_ptr(), part.data_ptr(), obs_stat.data_ptr(),
+            _stream())
+    return fitness, obs_stat
+
+
+def centered_rank_pairs(fitness):
+    """Centered rank of every row of ``fitness[P][n]`` in one launch:
+    ``ranks[p]`` is bit-identical to ``centered_rank(fitness[p])``, the
+    index-order tie-break included.  Only the O(n^2) comparison kernel is
+    batched, so ``n`` stops at 16384."""
+    ops = _require_ops()
+    _check(fitness, "fitness")
+    if fitness.dim() != 2:
+        raise ValueError("fitness must be [P, n], got %s"
+                         % (tuple(fitness.shape),))
+    P, n = fitness.shape
+    _check_pair_count(P)
+    if n < 2:
+        raise ValueError("n must be >= 2, got %d" % n)
+    if n > RANK_PAIRS_MAX_N:
+        raise ValueError("n = %d exceeds %d, the limit of the batched rank"
+                         % (n, RANK_PAIRS_MAX_N))
+    out = torch.empty_like(fitness)
+    with torch.cuda.device(fitness.device):
+        ops.centered_rank_pairs(fitness.data_ptr(), P, n, out.data_ptr(),
+                                _stream())
+    return out
+
+
+def es_grad_pairs(wpair, seeds, iteration):
+    """Noise-weighted gradient of every pair: ``grad[P][NPARAMS]`` from
+    ``wpair[P][pop/2]`` and the int32 ``seeds[P]``.  Row p is bit-identical
+    to ``es_grad(wpair[p], 0, pop/2, seed_p, iteration, device)``: the
+    same chunk split, partials summed in chunk order."""
+    ops = _require_ops()
+    _check_pairs_on((("wpair", wpair, torch.float32),
+                     ("seeds", seeds, torch.int32)), "wpair", wpair)
+    if wpair.dim() != 2 or wpair.shape[1] < 1:
+        raise ValueError("wpair must be [P, pop/2], got %s"
+                         % (tuple(wpair.shape),))
+    P, npairs = wpair.shape
+    _check_pair_count(P)
+    if tuple(seeds.shape) != (P,):
+        raise ValueError("seeds must be [%d], got %s"
+                         % (P, tuple(seeds.shape)))
+    if 2 * P * npairs >= 2 ** 31:
+        raise ValueError("P*pop = %d exceeds the launch grid"
+                         % (2 * P * npairs))
+    device = wpair.device
+    grad = torch.empty(P, NPARAMS, dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        chunks = ops.es_grad_chunks(npairs, NPARAMS)
+        part = _partial_buffer(device, P * chunks * NPARAMS)
+        ops.es_grad_pairs(wpair.data_ptr(), P, npairs, seeds.data_ptr(),
+                          int(iteration) & 0xFFFFFFFF, NPARAMS,
+                          part.data_ptr(), grad.data_ptr(), _stream())
+    return grad
+
+
 def ops_available():
     return _OPS is not None

@@ -39,6 +39,10 @@ class build_ext(_build_ext):
         out = os.path.join(ROOT, "fiber_amd", "_ops" + ext_suffix())
         srcs = [
             os.path.join(ROOT, "fiber_amd", "csrc", "ops", "es_kernels.hip"),
+            # includes the shared device code of es_kernels.hip, but is a
+            # translation unit of its own (register budget, see the file)
+            os.path.join(ROOT, "fiber_amd", "csrc", "ops",
+                         "es_pairs_kernels.hip"),
             os.path.join(ROOT, "fiber_amd", "csrc", "ops",
                          "conv_kernels.hip"),
             os.path.join(ROOT, "fiber_amd", "csrc", "ops", "bindings.cpp"),
