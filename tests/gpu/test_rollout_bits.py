@@ -15,6 +15,15 @@ and the t < horizon-1 branch) x member_offset in {0, 6} x sigma in
 underflow, the saturating path), all with a non-trivial obs normaliser and
 non-zero biases.
 
+The goldens come from the kernel itself, so they pin a build to its
+predecessor, not to the mathematics.  What ties them to an independent
+reading of the step loop is the fp64 oracle fiber_amd/es/rollout_oracle.py:
+tests/test_rollout_oracle.py holds the recorded episodes of
+eval_matrix_bits_k2m2_h17.npy to it (those whose 17 actions it calls
+decided), and tests/gpu/test_rollout_oracle_gpu.py holds the kernels of the
+current build to it, episode by episode, on inputs built like the ones
+here.
+
 Re-record (only ever from a build whose outputs are the accepted ones):
 
   python tests/gpu/test_rollout_bits.py --record
