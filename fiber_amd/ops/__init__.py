@@ -168,6 +168,10 @@ def centered_rank(fitness):
     identical output incl. the index-order tie-break."""
     _check(fitness, "fitness")
     n = fitness.numel()
+    if n < 2:
+        # rank / (n - 1) is 0/0 for a single member
+        raise ValueError("centered_rank needs at least 2 members, got %d"
+                         % n)
     ops = _require_ops()
     out = torch.empty_like(fitness)
     if n > 16384:

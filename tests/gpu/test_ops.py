@@ -176,3 +176,13 @@ class TestPhiloxDevice:
         # 2^-24 of a partial sum below 70*3, so < 70 * 210 * 6e-8 = 9e-4
         # worst case; the device noise itself matches to 1e-5 (above).
         assert (g1.cpu().double() - ref).abs().max().item() < 1e-3
+        # ... and per coordinate against the float64 draws, at the derived
+        # bound of update_oracle.grad_tol (about 2.6e-6 * sum |w*eps|)
+        from fiber_amd.es import update_oracle
+
+        g64, abs_sum = update_oracle.grad_fp64(
+            w_host.numpy(), begin, begin + npairs, 5, 2, ops.NPARAMS)
+        tol = update_oracle.grad_tol(
+            abs_sum, npairs, update_oracle.grad_chunks(npairs, ops.NPARAMS))
+        assert tol.max() < 1e-3
+        assert (np.abs(g1.cpu().double().numpy() - g64) <= tol).all()

@@ -13,6 +13,8 @@ import rollout_oracle_cases as C
 from fiber_amd.es import engine as es_engine
 from fiber_amd.es import philox_ref
 from fiber_amd.es import rollout_oracle as oracle
+# the float64 Box-Muller, shared with the update oracle's tests
+from fiber_amd.es.update_oracle import normals_fp64 as _normals_fp64
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CELLS = [(k, m) for k in range(C.K) for m in range(C.M)]
@@ -35,19 +37,6 @@ def test_tanh_emulation_error_is_the_documented_one():
                             "csrc", "ops", "es_kernels.hip")).read()
     assert "#define TWO_LOG2E 0x1.715476p+1f" in src
     assert "1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f)" in src
-
-
-def _normals_fp64(k0, k1, c0, c1, c2):
-    """Box-Muller in float64 from the float32 uniforms of fam_normal4."""
-    x = philox_ref.philox4x32_10(k0, k1, c0, c1, c2, np.uint32(0))
-    inv = np.float32(2.3283064365386963e-10)
-    u = [((xi.astype(np.float32) + np.float32(1.0)) * inv) for xi in x]
-    ang = [(np.float32(6.283185307179586) * ui).astype(np.float64)
-           for ui in (u[1], u[3])]
-    r = [np.sqrt(-2.0 * np.log(ui.astype(np.float64)))
-         for ui in (u[0], u[2])]
-    return np.stack([r[0] * np.cos(ang[0]), r[0] * np.sin(ang[0]),
-                     r[1] * np.cos(ang[1]), r[1] * np.sin(ang[1])], axis=-1)
 
 
 def test_numpy_draws_are_within_their_share_of_z_rel():
