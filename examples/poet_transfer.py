@@ -18,6 +18,14 @@ Prints one line per generation and, at the end, generations per second.
 steps of all pairs are one batched rollout / rank / gradient launch each
 instead of one ``ESEngine.step()`` per pair, with the same results (the
 ``gen`` lines are identical).
+
+``--reproduce`` (implies ``--batched``) replaces step 4 by POET's
+environment reproduction, ``fiber_amd.es.reproduce``: pairs whose own
+score reaches ``--repro-threshold`` propose perturbed child environments,
+the children that pass the minimal criterion are ranked by PATA-EC
+novelty against the active and archived environments, the most novel are
+admitted as new pairs seeded with the agent that does best on them, and
+past ``--max-pairs`` the oldest pairs retire to the archive.
 """
 
 import os as _os
@@ -35,7 +43,7 @@ import time
 import torch
 
 from fiber_amd.es import (ESConfig, ESEngine, ESPopulation, apply_transfers,
-                          make_env_params, select_transfers,
+                          make_env_params, reproduce, select_transfers,
                           transfer_matrix)
 
 
@@ -59,6 +67,20 @@ def main(argv=None):
     parser.add_argument("--margin", type=float, default=0.0)
     parser.add_argument("--batched", action="store_true",
                         help="advance all pairs together (ESPopulation)")
+    parser.add_argument("--reproduce", action="store_true",
+                        help="grow the population by environment "
+                             "reproduction (implies --batched)")
+    parser.add_argument("--max-pairs", type=int, default=12,
+                        help="--reproduce: pairs kept active; older ones "
+                             "retire to the archive")
+    parser.add_argument("--children", type=int, default=16,
+                        help="--reproduce: children proposed per generation")
+    parser.add_argument("--max-admit", type=int, default=2,
+                        help="--reproduce: children admitted per generation")
+    parser.add_argument("--repro-threshold", type=float,
+                        default=float("-inf"),
+                        help="--reproduce: own score a pair needs to "
+                             "propose children")
     args = parser.parse_args(argv)
 
     if not torch.cuda.is_available():
@@ -70,7 +92,7 @@ def main(argv=None):
                    seed=args.seed)
 
     envs = [perturbed_env(base, gen, 0.1) for _ in range(args.pairs)]
-    if args.batched:
+    if args.batched or args.reproduce:
         return run_batched(args, cfg, envs, gen, device)
     engines = []
     for i, env in enumerate(envs):
@@ -119,6 +141,7 @@ def run_batched(args, cfg, envs, gen, device):
     pop = ESPopulation(cfg, [args.seed + i for i in range(args.pairs)],
                        envs, device=device)
     total_transfers = 0
+    archive, next_seed, admitted_total = None, args.seed + args.pairs, 0
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for g in range(args.generations):
@@ -133,6 +156,34 @@ def run_batched(args, cfg, envs, gen, device):
         incumbent = diag.clone()
         for m, k in transfers:
             incumbent[m] = float(scores[k, m])
+        if args.reproduce:
+            # the returns of this toy lie in [-horizon, horizon]: a child
+            # is kept if its best agent neither fails nor has solved it
+            rec = reproduce(
+                pop, scores, archive=archive,
+                repro_threshold=args.repro_threshold,
+                n_children=args.children, mutate_scale=0.05, generator=gen,
+                mc_lo=0.0, mc_hi=0.98 * args.horizon, clip_lo=0.0,
+                clip_hi=float(args.horizon), knn=5,
+                max_admit=args.max_admit, max_pairs=args.max_pairs,
+                child_seeds=[next_seed + c for c in range(args.children)],
+                horizon=args.horizon, seed=args.seed, iteration=g)
+            next_seed += args.children
+            admitted_total += len(rec["admitted"])
+            if rec["retired"][2]:
+                old = archive or (rec["retired"][0][:0],
+                                  rec["retired"][1][:0])
+                archive = (torch.cat([old[0], rec["retired"][0]]),
+                           torch.cat([old[1], rec["retired"][1]]))
+            print("gen %d  transfers=%d  diag_mean=%.4f  parents=%d  "
+                  "passed=%d/%d  admitted=%s  donors=%s  retired=%d  "
+                  "pairs=%d  archive=%d"
+                  % (g, len(transfers), float(diag.mean()),
+                     len(rec["parents"]), int(rec["passed"].sum()),
+                     len(rec["parent_of"]), rec["admitted"], rec["donors"],
+                     len(rec["retired"][2]), pop.P,
+                     0 if archive is None else archive[0].shape[0]))
+            continue
         solved = int(torch.argmax(incumbent))
         envs[solved] = perturbed_env(envs[solved], gen, 0.05)
         pop.set_env(solved, *envs[solved])
@@ -142,6 +193,13 @@ def run_batched(args, cfg, envs, gen, device):
                  float(incumbent.max()), solved))
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.reproduce:
+        print("%d generations from %d to %d pairs in %.3f s: %.2f "
+              "generations/s, %d transfers, %d admissions in all "
+              "(batched, reproduce)"
+              % (args.generations, args.pairs, pop.P, dt,
+                 args.generations / dt, total_transfers, admitted_total))
+        return total_transfers
     print("%d generations of %d pairs in %.3f s: %.2f generations/s, "
           "%d transfers in all (batched)"
           % (args.generations, args.pairs, dt, args.generations / dt,

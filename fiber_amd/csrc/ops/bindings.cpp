@@ -52,6 +52,12 @@ extern "C" __global__ void es_grad_pairs(const float*, int, int,
 extern "C" __global__ void es_grad_reduce_pairs(const float*, int, int,
                                                 float*);
 // conv policy pipeline (conv_kernels.hip)
+// PATA-EC novelty kernels (poet_kernels.hip)
+extern "C" __global__ void pata_ec_codes(const float*, int, int, int, float,
+                                         float, int16_t*);
+extern "C" __global__ void pata_ec_knn(const int16_t*, int, int, int, int,
+                                       int, int*, float*);
+
 extern "C" __global__ void es_perturb(const float*, int, int, float,
                                       uint32_t, const uint32_t*, int,
                                       __hip_bfloat16*, unsigned char*,
@@ -422,6 +428,34 @@ static void launch_conv_head_env(uintptr_t wpert, uintptr_t act3,
   check(hipGetLastError(), "conv_head_env launch");
 }
 
+// scores[K][M] -> codes[M][Kpad]: one block per 16 columns.  The caps are
+// those of the kernels' LDS arrays (poet_kernels.hip).
+static void launch_pata_ec_codes(uintptr_t scores, int K, int M, int Kpad,
+                                 double lo, double hi, uintptr_t codes,
+                                 uintptr_t stream) {
+  if (K < 2 || K > 512 || M < 1 || Kpad != (K + 7) / 8 * 8)
+    throw std::runtime_error("pata_ec_codes: bad K, M or Kpad");
+  hipLaunchKernelGGL(pata_ec_codes, dim3((unsigned)((M + 15) / 16)),
+                     dim3(256), 0, (hipStream_t)stream,
+                     (const float*)scores, K, M, Kpad, (float)lo, (float)hi,
+                     (int16_t*)codes);
+  check(hipGetLastError(), "pata_ec_codes launch");
+}
+
+// codes rows [n_ref, n_ref + Q) against rows [0, n_ref): 4 queries per
+// block; k is already min(k, n_ref).
+static void launch_pata_ec_knn(uintptr_t codes, int Kpad, int K, int n_ref,
+                               int Q, int k, uintptr_t knn_d2,
+                               uintptr_t novelty, uintptr_t stream) {
+  if (K < 2 || K > 512 || Kpad != (K + 7) / 8 * 8 || n_ref < 1 || Q < 1 ||
+      k < 1 || k > 64 || k > n_ref)
+    throw std::runtime_error("pata_ec_knn: bad K, Kpad, n_ref, Q or k");
+  hipLaunchKernelGGL(pata_ec_knn, dim3((unsigned)((Q + 3) / 4)), dim3(256),
+                     0, (hipStream_t)stream, (const int16_t*)codes, Kpad, K,
+                     n_ref, Q, k, (int*)knn_d2, (float*)novelty);
+  check(hipGetLastError(), "pata_ec_knn launch");
+}
+
 PYBIND11_MODULE(_ops, m) {
   m.doc() = "fiber_amd CDNA4 ES kernels (gfx950)";
   m.attr("NPARAMS") = NPARAMS_HOST;
@@ -456,6 +490,13 @@ PYBIND11_MODULE(_ops, m) {
   m.def("es_grad_pairs", &launch_grad_pairs, py::arg("wpair"), py::arg("P"),
         py::arg("npairs"), py::arg("seeds"), py::arg("iter"),
         py::arg("nparams"), py::arg("grad_part"), py::arg("grad"),
+        py::arg("stream"));
+  m.def("pata_ec_codes", &launch_pata_ec_codes, py::arg("scores"),
+        py::arg("K"), py::arg("M"), py::arg("Kpad"), py::arg("lo"),
+        py::arg("hi"), py::arg("codes"), py::arg("stream"));
+  m.def("pata_ec_knn", &launch_pata_ec_knn, py::arg("codes"),
+        py::arg("Kpad"), py::arg("K"), py::arg("n_ref"), py::arg("Q"),
+        py::arg("k"), py::arg("knn_d2"), py::arg("novelty"),
         py::arg("stream"));
   m.def("centered_rank_sorted_workspace", &centered_rank_sorted_workspace,
         py::arg("n"));

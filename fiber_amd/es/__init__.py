@@ -8,6 +8,10 @@ from .engine import (  # noqa: F401
 from .population import ESPopulation  # noqa: F401
 from .poet import (  # noqa: F401
     apply_transfers,
+    minimal_criterion,
+    propose_children,
+    reproduce,
+    select_children,
     select_transfers,
     transfer_matrix,
 )

@@ -84,3 +84,183 @@ def apply_transfers(engines, transfers):
             getattr(dst, f).copy_(donors[k][f])
         dst.adam_m.zero_()
         dst.adam_v.zero_()
+
+
+# ---------------------------------------------------------------------------
+# Environment reproduction: the open-ended half of POET.
+#
+#     record = reproduce(pop, scores, archive=archive, ...)
+#
+# proposes child environments from the pairs that are ready, keeps those
+# that pass the minimal criterion (neither too easy nor too hard), ranks
+# them by PATA-EC novelty against the active and archived environments
+# (ops.env_novelty), admits the most novel as new pairs seeded with the
+# agent that does best on them, and retires the oldest pairs when the
+# population is over capacity.
+# ---------------------------------------------------------------------------
+
+
+def propose_children(env_A, env_B, parents, n_children, scale, generator):
+    """``n_children`` perturbed copies of the environments ``env_A[P][4][4]``,
+    ``env_B[P][4]``, taking the parents round-robin from ``parents``.
+
+    Host side and seeded: the draws come from the CPU ``generator`` in a
+    fixed order (child by child, env_A then env_B).  Returns
+    ``(child_A[C][4][4], child_B[C][4], parent_of[C])`` with CPU tensors
+    and a list of parent indices."""
+    parents = [int(p) for p in parents]
+    n_children = int(n_children)
+    if n_children < 0:
+        raise ValueError("n_children must be >= 0, got %d" % n_children)
+    if n_children and not parents:
+        raise ValueError("propose_children needs at least one parent")
+    P = env_A.shape[0]
+    for p in parents:
+        if not 0 <= p < P:
+            raise IndexError("parent %d outside 0..%d" % (p, P - 1))
+    env_A = env_A.detach().to("cpu", torch.float32)
+    env_B = env_B.detach().to("cpu", torch.float32)
+    child_A = torch.empty((n_children,) + tuple(env_A.shape[1:]))
+    child_B = torch.empty((n_children,) + tuple(env_B.shape[1:]))
+    parent_of = []
+    for c in range(n_children):
+        p = parents[c % len(parents)]
+        child_A[c] = env_A[p] + scale * torch.randn(env_A[p].shape,
+                                                    generator=generator)
+        child_B[c] = env_B[p] + scale * torch.randn(env_B[p].shape,
+                                                    generator=generator)
+        parent_of.append(p)
+    return child_A, child_B, parent_of
+
+
+def minimal_criterion(child_scores, lo, hi):
+    """bool ``[C]`` on the device of ``child_scores[K][C]``: child c passes
+    if the best non-NaN score any agent reaches on it lies in ``[lo, hi]``,
+    so it is neither too hard nor too easy.  An all-NaN column fails."""
+    if child_scores.dim() != 2:
+        raise ValueError("child_scores must be [K, C], got %s"
+                         % (tuple(child_scores.shape),))
+    if child_scores.shape[0] == 0:
+        return torch.zeros(child_scores.shape[1], dtype=torch.bool,
+                           device=child_scores.device)
+    neg_inf = torch.full_like(child_scores, float("-inf"))
+    isnan = torch.isnan(child_scores)
+    best = torch.where(isnan, neg_inf, child_scores).max(dim=0).values
+    return (~isnan.all(dim=0)) & (best >= lo) & (best <= hi)
+
+
+def select_children(novelty, passed, max_admit):
+    """Indices of at most ``max_admit`` children, by novelty descending.
+    Only children with ``passed`` set are considered, a NaN novelty never
+    wins and ties go to the lowest index.  Returns a list of ints."""
+    nov = novelty.detach().to("cpu", torch.float64).tolist()
+    ok = passed.detach().to("cpu").tolist()
+    if len(nov) != len(ok):
+        raise ValueError("%d novelties but %d pass flags"
+                         % (len(nov), len(ok)))
+    max_admit = int(max_admit)
+    if max_admit < 0:
+        raise ValueError("max_admit must be >= 0, got %d" % max_admit)
+    cand = [c for c in range(len(nov)) if ok[c] and nov[c] == nov[c]]
+    cand.sort(key=lambda c: (-nov[c], c))
+    return cand[:max_admit]
+
+
+def _best_agent(column):
+    """Row of the best score in a column (list of floats): the lowest
+    index wins a tie, NaN never wins; None if every score is NaN."""
+    best_k, best = None, None
+    for k, v in enumerate(column):
+        if v != v:
+            continue
+        if best is None or v > best:
+            best_k, best = k, v
+    return best_k
+
+
+def _empty_record(pop):
+    n = pop.cfg.obs_dim
+    return {
+        "parents": [], "parent_of": [], "admitted": [], "donors": [],
+        "novelty": torch.empty(0), "passed": torch.zeros(0, dtype=torch.bool),
+        "child_A": torch.empty(0, n, n), "child_B": torch.empty(0, n),
+        "retired": (torch.empty(0, n, n), torch.empty(0, n), []),
+    }
+
+
+def reproduce(pop, scores, *, archive=None, repro_threshold, n_children,
+              mutate_scale, generator, mc_lo, mc_hi, clip_lo, clip_hi, knn,
+              max_admit, max_pairs, child_seeds, horizon, seed, iteration):
+    """One POET reproduction step on an ``ESPopulation``.
+
+    ``scores`` is this generation's ``pop.transfer_matrix``; ``archive`` is
+    ``None`` or ``(env_A[R][4][4], env_B[R][4])`` of retired environments;
+    ``child_seeds[c]`` is the seed (noise stream) child c gets if admitted.
+
+    1. parents: pairs whose own score ``scores[p][p] >= repro_threshold``;
+       none gives an empty record;
+    2. ``propose_children`` and one ``es_eval_matrix`` launch of all P
+       policies on active + archived + child environments;
+    3. ``minimal_criterion`` on the child columns and ``ops.env_novelty``
+       with ``n_ref = P + |archive|``;
+    4. ``select_children`` admits up to ``max_admit``;
+    5. the donor of an admitted child is the best agent on its column;
+    6. ``pop.add_pairs``;
+    7. over ``max_pairs`` the lowest indices (the oldest pairs) are
+       removed and returned for the caller's archive.
+
+    Returns a dict: ``parents``, ``parent_of``, ``admitted`` (child
+    indices), ``donors``, ``novelty[C]`` and ``passed[C]`` (CPU), the
+    proposed ``child_A`` / ``child_B``, and ``retired`` = ``(env_A, env_B,
+    seeds)`` as ``remove_pairs`` returns it.  The device is waited for
+    once, when the child scores, pass mask and novelties come to the
+    host."""
+    P = pop.P
+    if tuple(scores.shape) != (P, P):
+        raise ValueError("scores must be [%d, %d], got %s"
+                         % (P, P, tuple(scores.shape)))
+    n_children, max_admit = int(n_children), int(max_admit)
+    max_pairs = int(max_pairs)
+    if max_pairs < 1:
+        raise ValueError("max_pairs must be >= 1, got %d" % max_pairs)
+    if len(child_seeds) < n_children:
+        raise ValueError("%d child_seeds for %d children"
+                         % (len(child_seeds), n_children))
+    diag = scores.diagonal().detach().to("cpu", torch.float64).tolist()
+    parents = [p for p in range(P) if diag[p] >= repro_threshold]
+    if not parents or n_children < 1:
+        return _empty_record(pop)
+
+    child_A, child_B, parent_of = propose_children(
+        pop.env_A, pop.env_B, parents, n_children, mutate_scale, generator)
+    dev = pop.device
+    parts_A, parts_B = [pop.env_A], [pop.env_B]
+    n_arch = 0
+    if archive is not None and archive[0].shape[0]:
+        n_arch = archive[0].shape[0]
+        parts_A.append(archive[0].to(dev, torch.float32))
+        parts_B.append(archive[1].to(dev, torch.float32))
+    parts_A.append(child_A.to(dev))
+    parts_B.append(child_B.to(dev))
+    all_scores = ops.es_eval_matrix(
+        pop.theta, pop.obs_mu, pop.obs_nu, torch.cat(parts_A).contiguous(),
+        torch.cat(parts_B).contiguous(), seed, iteration, horizon)
+    n_ref = P + n_arch
+    child_scores = all_scores[:, n_ref:]
+    passed = minimal_criterion(child_scores, mc_lo, mc_hi)
+    novelty = ops.env_novelty(all_scores, n_ref, knn, clip_lo, clip_hi)
+
+    child_cpu = child_scores.to("cpu", torch.float64)  # the host sync
+    passed, novelty = passed.cpu(), novelty.cpu()
+    admitted = select_children(novelty, passed, max_admit)
+    donors = [_best_agent(child_cpu[:, c].tolist()) for c in admitted]
+    pop.add_pairs([child_seeds[c] for c in admitted],
+                  [(child_A[c], child_B[c]) for c in admitted], donors)
+    retired = _empty_record(pop)["retired"]
+    if pop.P > max_pairs:
+        retired = pop.remove_pairs(range(pop.P - max_pairs))
+    return {
+        "parents": parents, "parent_of": parent_of, "admitted": admitted,
+        "donors": donors, "novelty": novelty, "passed": passed,
+        "child_A": child_A, "child_B": child_B, "retired": retired,
+    }

@@ -157,6 +157,80 @@ class ESPopulation:
         self.adam_m[dst] = 0.0
         self.adam_v[dst] = 0.0
 
+    # -- POET reproduction: the population grows and shrinks ---------------
+    _ROW_FIELDS = _STATE_FIELDS + ("obs_mu", "obs_nu", "env_A", "env_B")
+
+    def add_pairs(self, seeds, env_params, donors):
+        """Append ``len(seeds)`` pairs.  New pair i takes the policy rows
+        (theta and the obs statistics) of existing pair ``donors[i]``, read
+        from the state before the call, with zero Adam moments, its own
+        seed (noise stream) ``seeds[i]`` and environment ``env_params[i]``
+        = ``(env_A, env_B)``.  ``t_step`` stays shared, as in
+        ``apply_transfers``.  From here on the new pair is, bit for bit,
+        an ``ESEngine(replace(cfg, seed=seeds[i]), env_params=...)`` loaded
+        with the donor's ``engine_state`` and the moments zeroed."""
+        seeds = [int(s) for s in seeds]
+        donors = [int(d) for d in donors]
+        env_params = list(env_params)
+        if not (len(seeds) == len(env_params) == len(donors)):
+            raise ValueError("%d seeds, %d env_params, %d donors"
+                             % (len(seeds), len(env_params), len(donors)))
+        for d in donors:
+            if not 0 <= d < self.P:
+                raise IndexError("donor %d outside 0..%d" % (d, self.P - 1))
+        n = self.cfg.obs_dim
+        for env_A, env_B in env_params:
+            if tuple(env_A.shape) != (n, n) or tuple(env_B.shape) != (n,):
+                raise ValueError(
+                    "env_params must be (env_A[%d][%d], env_B[%d])"
+                    % (n, n, n))
+        if not seeds:
+            return
+        src = torch.tensor(donors, device=self.device)
+        for name in _POLICY_FIELDS:
+            field = getattr(self, name)
+            setattr(self, name, torch.cat([field, field[src]]).contiguous())
+        for name in ("adam_m", "adam_v"):
+            field = getattr(self, name)
+            zeros = field.new_zeros((len(seeds),) + tuple(field.shape[1:]))
+            setattr(self, name, torch.cat([field, zeros]).contiguous())
+        new_A = torch.stack([a.detach().to(torch.float32)
+                             for a, _b in env_params]).to(self.device)
+        new_B = torch.stack([b.detach().to(torch.float32)
+                             for _a, b in env_params]).to(self.device)
+        self.env_A = torch.cat([self.env_A, new_A]).contiguous()
+        self.env_B = torch.cat([self.env_B, new_B]).contiguous()
+        self._set_seeds(self.seeds + seeds)
+
+    def remove_pairs(self, indices):
+        """Drop the pairs ``indices`` (the others keep their order and
+        every bit of their state).  Returns ``(env_A[R][4][4],
+        env_B[R][4], seeds)`` of the removed pairs in ascending index
+        order, for the caller's archive."""
+        drop = sorted({int(i) for i in indices})
+        for i in drop:
+            if not 0 <= i < self.P:
+                raise IndexError("pair %d outside 0..%d" % (i, self.P - 1))
+        if len(drop) >= self.P:
+            raise ValueError("remove_pairs would leave no pair")
+        gone = set(drop)
+        keep = [p for p in range(self.P) if p not in gone]
+        drop_idx = torch.tensor(drop, dtype=torch.long, device=self.device)
+        keep_idx = torch.tensor(keep, dtype=torch.long, device=self.device)
+        removed = (self.env_A[drop_idx], self.env_B[drop_idx],
+                   [self.seeds[i] for i in drop])
+        if drop:
+            for name in self._ROW_FIELDS:
+                setattr(self, name,
+                        getattr(self, name)[keep_idx].contiguous())
+            self._set_seeds([self.seeds[p] for p in keep])
+        return removed
+
+    def _set_seeds(self, seeds):
+        self.seeds = list(seeds)
+        self.P = len(self.seeds)
+        self._seeds_dev = ops.pair_seeds(self.seeds, self.device)
+
     def set_env(self, p, env_A, env_B):
         """Replace pair p's environment (copies, like ESEngine)."""
         n = self.cfg.obs_dim

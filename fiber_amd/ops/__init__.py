@@ -407,5 +407,98 @@ def es_grad_pairs(wpair, seeds, iteration):
     return grad
 
 
+# ---------------------------------------------------------------------------
+# PATA-EC environment novelty (poet_kernels.hip): integer rank codes per
+# environment and exact k-nearest-neighbour squared distances between them.
+# ---------------------------------------------------------------------------
+
+PATA_K_MAX = 512    # D2 <= K * 4 (K-1)^2 = 534,773,760 < 2^31 up to here
+PATA_KNN_MAX = 64   # neighbours per query
+
+
+def _check_pata_scores(scores, clip_lo, clip_hi):
+    _check(scores, "scores")
+    if scores.dim() != 2:
+        raise ValueError("scores must be [K, M], got %s"
+                         % (tuple(scores.shape),))
+    K, M = scores.shape
+    if K < 2 or K > PATA_K_MAX:
+        raise ValueError("K must be in [2, %d], got %d" % (PATA_K_MAX, K))
+    if M < 1:
+        raise ValueError("scores has no columns")
+    clip_lo, clip_hi = float(clip_lo), float(clip_hi)
+    if not clip_lo <= clip_hi:  # also refuses a NaN bound
+        raise ValueError("clip_lo must be <= clip_hi, got %r, %r"
+                         % (clip_lo, clip_hi))
+    return K, M, clip_lo, clip_hi
+
+
+def _launch_pata_codes(ops, scores, K, M, clip_lo, clip_hi):
+    Kpad = (K + 7) // 8 * 8
+    codes = torch.empty(M, Kpad, dtype=torch.int16, device=scores.device)
+    ops.pata_ec_codes(scores.data_ptr(), K, M, Kpad, clip_lo, clip_hi,
+                      codes.data_ptr(), _stream())
+    return codes
+
+
+def pata_ec_codes(scores, clip_lo, clip_hi):
+    """PATA-EC rank codes of every environment.
+
+    ``scores[K][M]`` (row = agent, column = environment, as
+    ``es_eval_matrix`` returns it) becomes int16 ``codes[M][Kpad]``,
+    environment-major, ``Kpad`` = K rounded up to 8 with the pad entries
+    0.  Column m is clipped to ``[clip_lo, clip_hi]`` (NaN counts as
+    ``clip_lo``) and ``code[i] = 2 #{j: c_j < c_i} + #{j: c_j == c_i} - 1``,
+    twice the mid-rank: tied scores, which clipping makes common, share a
+    code.
+
+    TypeError for dtype, device or contiguity, ValueError for shape,
+    ``K`` outside ``[2, 512]`` or ``clip_lo > clip_hi``, all before the
+    launch."""
+    ops = _require_ops()
+    K, M, clip_lo, clip_hi = _check_pata_scores(scores, clip_lo, clip_hi)
+    with torch.cuda.device(scores.device):
+        return _launch_pata_codes(ops, scores, K, M, clip_lo, clip_hi)
+
+
+def env_novelty(scores, n_ref, k, clip_lo, clip_hi, return_neighbours=False):
+    """PATA-EC novelty of the environments in columns ``[n_ref, M)`` of
+    ``scores[K][M]`` against the reference environments in columns
+    ``[0, n_ref)``.
+
+    With the codes of ``pata_ec_codes``, ``D2(q, r)`` is the exact int32
+    squared Euclidean distance between two code rows, ``knn_d2[Q][k']``
+    the ``k' = min(k, n_ref)`` smallest of a query in ascending order, and
+    ``novelty[q] = sum_j sqrt(knn_d2[q][j]) / (k' * 2 * (K - 1))``, the
+    mean Euclidean distance to the k' nearest rank vectors with the ranks
+    scaled to [0, 1], summed in a fixed order (two calls give the same
+    bits).  Returns ``novelty[Q]`` (fp32),
+    or ``(novelty, knn_d2)``.
+
+    Validation as in ``pata_ec_codes``, plus ValueError unless
+    ``1 <= k <= 64``, ``n_ref >= 1`` and ``Q = M - n_ref >= 1``."""
+    ops = _require_ops()
+    K, M, clip_lo, clip_hi = _check_pata_scores(scores, clip_lo, clip_hi)
+    n_ref, k = int(n_ref), int(k)
+    if k < 1 or k > PATA_KNN_MAX:
+        raise ValueError("k must be in [1, %d], got %d" % (PATA_KNN_MAX, k))
+    if n_ref < 1:
+        raise ValueError("n_ref must be >= 1, got %d" % n_ref)
+    Q = M - n_ref
+    if Q < 1:
+        raise ValueError("no query columns: M = %d, n_ref = %d" % (M, n_ref))
+    k_eff = min(k, n_ref)
+    device = scores.device
+    with torch.cuda.device(device):
+        codes = _launch_pata_codes(ops, scores, K, M, clip_lo, clip_hi)
+        knn_d2 = torch.empty(Q, k_eff, dtype=torch.int32, device=device)
+        novelty = torch.empty(Q, dtype=torch.float32, device=device)
+        ops.pata_ec_knn(codes.data_ptr(), codes.shape[1], K, n_ref, Q, k_eff,
+                        knn_d2.data_ptr(), novelty.data_ptr(), _stream())
+    if return_neighbours:
+        return novelty, knn_d2
+    return novelty
+
+
 def ops_available():
     return _OPS is not None

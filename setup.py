@@ -43,6 +43,10 @@ class build_ext(_build_ext):
             # translation unit of its own (register budget, see the file)
             os.path.join(ROOT, "fiber_amd", "csrc", "ops",
                          "es_pairs_kernels.hip"),
+            # PATA-EC novelty kernels: shares nothing with the rollout
+            # kernels and stays out of their register allocation
+            os.path.join(ROOT, "fiber_amd", "csrc", "ops",
+                         "poet_kernels.hip"),
             os.path.join(ROOT, "fiber_amd", "csrc", "ops",
                          "conv_kernels.hip"),
             os.path.join(ROOT, "fiber_amd", "csrc", "ops", "bindings.cpp"),
