@@ -93,17 +93,29 @@ _ULP = {"bf16": ulp_bf16, "e4m3": ulp_e4m3}
 # ---------------------------------------------------------------------------
 
 
-def obs_reference(znoise_u8, state, gtab_bf16):
+def obs_reference(znoise_u8, state, gtab_bf16, fused=False):
     """obs[E][84][84][4] as conv_layer1 builds it in LDS:
     e4m3(e4m3val(znoise[be % 16]) + state[be][ic] * g) in fp32, RNE.
-    Returned as the fp32 values of the e4m3 bytes."""
+    Returned as the fp32 values of the e4m3 bytes.
+
+    The kernel's source is ``noise + s * g``; the compiler may contract it
+    to one fma.  ``fused=False`` rounds the product and the sum (two fp32
+    roundings), ``fused=True`` rounds the exact sum once (the 32-bit
+    product of an fp32 and a bf16 number, and its sum with a 4-bit e4m3
+    number, are exact in fp64).  Both are legal fp32 evaluations; they give
+    different e4m3 bytes only where an e4m3 midpoint lies within one fp32
+    ulp of the sum (a few pixels per million off the 1/8 grid)."""
     state = state.to(torch.float32)
     nenv = state.shape[0]
     noise = e4m3_val(znoise_u8).to(torch.float32).reshape(
         CENV, IMG * IMG, 4)
     rows = torch.arange(nenv) % CENV
     g = gtab_bf16.to(torch.float32).reshape(1, IMG * IMG, 1)
-    r = noise[rows] + state[:, None, :] * g
+    if fused:
+        r = (noise[rows].double()
+             + state[:, None, :].double() * g.double()).to(torch.float32)
+    else:
+        r = noise[rows] + state[:, None, :] * g
     return r.to(_F8).to(torch.float32).reshape(nenv, IMG, IMG, 4)
 
 
@@ -150,14 +162,27 @@ def fc_reference(act2_u8, w3_fp8_u8, b3_bf16):
     return pre[:, 0], absdot[:, 0]
 
 
+def env_step_reference(state, action, env_A, env_B, racc):
+    """The env half of conv_head_env in fp64 for given actions:
+    state[E][4], action[E], racc[E] -> (new_state, new_racc).  The
+    kernel's fp32 constants are used at their fp32 values."""
+    f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))  # noqa
+    force = (action.to(torch.float64) - 2.5) * f32(0.4)
+    s = to_f64(state).reshape(-1, 4)
+    drive = torch.tanh(s @ to_f64(env_A).reshape(4, 4).T)
+    snew = (f32(0.97) * s + f32(0.08) * drive
+            + f32(0.05) * to_f64(env_B).reshape(1, 4) * force[:, None])
+    racc_new = to_f64(racc).reshape(-1) + 1.0 - f32(0.1) * (
+        snew * snew).sum(dim=1)
+    return snew, racc_new
+
+
 def head_env_reference(act3_bf16, w4, b4, state, env_A, env_B, racc):
     """conv_head_env in fp64.  act3[E][256], w4[M][6][256], b4[M][6],
     state[E][4], racc[E].  Returns (logits, action, new_state, new_racc,
     bound): the action is the FIRST maximum (the kernel's strict ``>``),
     and bound[E][6] = 256 * 2^-23 * sum|w*h| + 2^-23 |b| is the
-    worst-case fp32 error of a logit.  The kernel's fp32 constants are
-    used at their fp32 values."""
-    f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))  # noqa
+    worst-case fp32 error of a logit."""
     h = to_f64(act3_bf16).reshape(-1, 1, 256)
     w = to_f64(w4).reshape(-1, 6, 256)
     b = to_f64(b4).reshape(-1, 6)
@@ -166,13 +191,7 @@ def head_env_reference(act3_bf16, w4, b4, state, env_A, env_B, racc):
     bound = 256 * 2.0 ** -23 * absdot + 2.0 ** -23 * \
         b.abs().repeat_interleave(CENV, dim=0)
     action = torch.from_numpy(logits.numpy().argmax(axis=1))  # first max
-    force = (action.to(torch.float64) - 2.5) * f32(0.4)
-    s = to_f64(state).reshape(-1, 4)
-    drive = torch.tanh(s @ to_f64(env_A).reshape(4, 4).T)
-    snew = (f32(0.97) * s + f32(0.08) * drive
-            + f32(0.05) * to_f64(env_B).reshape(1, 4) * force[:, None])
-    racc_new = to_f64(racc).reshape(-1) + 1.0 - f32(0.1) * (
-        snew * snew).sum(dim=1)
+    snew, racc_new = env_step_reference(state, action, env_A, env_B, racc)
     return logits, action, snew, racc_new, bound
 
 

@@ -58,6 +58,8 @@ class TestConvPipeline:
             assert (got - want).abs().max().item() < 5e-3
 
     def test_rollout_vs_fp32_reference(self):
+        """Coarse; the chain is checked step by step in
+        tests/gpu/test_conv_rollout_chain_gpu.py."""
         device = torch.device("cuda")
         cfg = ConvESConfig(pop_per_gpu=2, horizon=3)
         eng = ConvESEngine(cfg, ctx=None, device=device)
