@@ -51,6 +51,17 @@ extern "C" __global__ void es_grad_pairs(const float*, int, int,
                                          float*);
 extern "C" __global__ void es_grad_reduce_pairs(const float*, int, int,
                                                 float*);
+// novelty-search kernels (ns_kernels.hip)
+extern "C" __global__ void es_rollout_mlp_bc(
+    const float*, float, uint32_t, uint32_t, int, int, const float*,
+    const float*, const float*, const float*, float*, float*, float*, float*,
+    float*);
+extern "C" __global__ void es_eval_bc(const float*, const float*,
+                                      const float*, const float*,
+                                      const float*, uint32_t, uint32_t, int,
+                                      int, float*, float*, float*, float*);
+extern "C" __global__ void bc_knn_novelty(const float*, int, const float*,
+                                          int, int, float*, float*);
 // conv policy pipeline (conv_kernels.hip)
 // PATA-EC novelty kernels (poet_kernels.hip)
 extern "C" __global__ void pata_ec_codes(const float*, int, int, int, float,
@@ -326,6 +337,75 @@ static void launch_logits_reduce_probe(uintptr_t p0, uintptr_t p1,
   check(hipGetLastError(), "logits_reduce_probe launch");
 }
 
+// ---- novelty-search launchers --------------------------------------------
+// The limits of bc_knn_novelty (ns_kernels.hip): neighbours kept per query
+// and archive rows per LDS tile.
+#define BC_KNN_MAX_HOST 16
+#define BC_KNN_TILE_HOST 1024
+
+// launch_rollout with a BC per member; final_states == 0 skips that store.
+static void launch_rollout_bc(uintptr_t theta, double sigma, uint32_t seed,
+                              uint32_t iter, int horizon, int member_offset,
+                              int pop_shard, uintptr_t obs_mu,
+                              uintptr_t obs_nu, uintptr_t env_A,
+                              uintptr_t env_B, uintptr_t fitness,
+                              uintptr_t obs_stat_part, uintptr_t obs_stat,
+                              uintptr_t bc, uintptr_t final_states,
+                              uintptr_t stream) {
+  if (pop_shard <= 0) return;
+  if (horizon < 1)
+    throw std::runtime_error("es_rollout_mlp_bc: horizon must be >= 1");
+  hipLaunchKernelGGL(es_rollout_mlp_bc, dim3(pop_shard), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)theta, (float)sigma,
+                     seed, iter, horizon, member_offset,
+                     (const float*)obs_mu, (const float*)obs_nu,
+                     (const float*)env_A, (const float*)env_B,
+                     (float*)fitness, (float*)obs_stat_part,
+                     (float*)obs_stat, (float*)bc, (float*)final_states);
+  check(hipGetLastError(), "es_rollout_mlp_bc launch");
+  hipLaunchKernelGGL(obs_stat_reduce, dim3(2 * OBS_HOST), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)obs_stat_part,
+                     pop_shard, (float*)obs_stat);
+  check(hipGetLastError(), "obs_stat_reduce launch");
+}
+
+// launch_eval_matrix with a BC per cell; episodes / final_states == 0 skip
+// those stores.
+static void launch_eval_bc(uintptr_t thetas, uintptr_t obs_mu,
+                           uintptr_t obs_nu, uintptr_t env_A,
+                           uintptr_t env_B, uint32_t seed, uint32_t iter,
+                           int horizon, int K, int M, uintptr_t scores,
+                           uintptr_t episodes, uintptr_t bc,
+                           uintptr_t final_states, uintptr_t stream) {
+  if (K <= 0 || M <= 0) return;
+  const long long cells = (long long)K * (long long)M;
+  if (cells > 0x7FFFFFFFLL)
+    throw std::runtime_error("es_eval_bc: K*M exceeds the grid limit");
+  if (horizon < 1)
+    throw std::runtime_error("es_eval_bc: horizon must be >= 1");
+  hipLaunchKernelGGL(es_eval_bc, dim3((unsigned)cells), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)thetas,
+                     (const float*)obs_mu, (const float*)obs_nu,
+                     (const float*)env_A, (const float*)env_B, seed, iter,
+                     horizon, M, (float*)scores, (float*)episodes,
+                     (float*)bc, (float*)final_states);
+  check(hipGetLastError(), "es_eval_bc launch");
+}
+
+// N queries against R archive rows, one thread per query; knn_d2 == 0
+// skips the neighbour store.
+static void launch_bc_knn_novelty(uintptr_t bc, int N, uintptr_t archive,
+                                  int R, int k, uintptr_t novelty,
+                                  uintptr_t knn_d2, uintptr_t stream) {
+  if (N < 1 || R < 1 || k < 1 || k > BC_KNN_MAX_HOST || k > R)
+    throw std::runtime_error("bc_knn_novelty: bad N, R or k");
+  hipLaunchKernelGGL(bc_knn_novelty, dim3((unsigned)((N + 255) / 256)),
+                     dim3(256), 0, (hipStream_t)stream, (const float*)bc, N,
+                     (const float*)archive, R, k, (float*)novelty,
+                     (float*)knn_d2);
+  check(hipGetLastError(), "bc_knn_novelty launch");
+}
+
 // ---- conv pipeline launchers ---------------------------------------------
 
 static void launch_perturb(uintptr_t theta, int nparams, int np_pad,
@@ -491,6 +571,23 @@ PYBIND11_MODULE(_ops, m) {
         py::arg("npairs"), py::arg("seeds"), py::arg("iter"),
         py::arg("nparams"), py::arg("grad_part"), py::arg("grad"),
         py::arg("stream"));
+  m.attr("BC_KNN_MAX") = BC_KNN_MAX_HOST;
+  m.attr("BC_KNN_TILE") = BC_KNN_TILE_HOST;
+  m.def("es_rollout_mlp_bc", &launch_rollout_bc, py::arg("theta"),
+        py::arg("sigma"), py::arg("seed"), py::arg("iter"),
+        py::arg("horizon"), py::arg("member_offset"), py::arg("pop_shard"),
+        py::arg("obs_mu"), py::arg("obs_nu"), py::arg("env_A"),
+        py::arg("env_B"), py::arg("fitness"), py::arg("obs_stat_part"),
+        py::arg("obs_stat"), py::arg("bc"), py::arg("final_states"),
+        py::arg("stream"));
+  m.def("es_eval_bc", &launch_eval_bc, py::arg("thetas"), py::arg("obs_mu"),
+        py::arg("obs_nu"), py::arg("env_A"), py::arg("env_B"),
+        py::arg("seed"), py::arg("iter"), py::arg("horizon"), py::arg("K"),
+        py::arg("M"), py::arg("scores"), py::arg("episodes"), py::arg("bc"),
+        py::arg("final_states"), py::arg("stream"));
+  m.def("bc_knn_novelty", &launch_bc_knn_novelty, py::arg("bc"),
+        py::arg("N"), py::arg("archive"), py::arg("R"), py::arg("k"),
+        py::arg("novelty"), py::arg("knn_d2"), py::arg("stream"));
   m.def("pata_ec_codes", &launch_pata_ec_codes, py::arg("scores"),
         py::arg("K"), py::arg("M"), py::arg("Kpad"), py::arg("lo"),
         py::arg("hi"), py::arg("codes"), py::arg("stream"));

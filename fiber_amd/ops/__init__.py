@@ -500,5 +500,214 @@ def env_novelty(scores, n_ref, k, clip_lo, clip_hi, return_neighbours=False):
     return novelty
 
 
+# ---------------------------------------------------------------------------
+# Novelty search (ns_kernels.hip): the rollout kernels with a behaviour
+# characterisation (BC) per member or cell, and k-nearest-neighbour novelty
+# of BCs against an archive.  The BC is the mean over the 64 episodes of the
+# final state s_H, 4 floats.
+# ---------------------------------------------------------------------------
+
+BC_DIM = OBS_DIM
+BC_KNN_MAX = _OPS.BC_KNN_MAX if _OPS else 16     # neighbours per query
+BC_KNN_TILE = _OPS.BC_KNN_TILE if _OPS else 1024  # archive rows per LDS tile
+
+
+def es_rollout_mlp_bc(theta, sigma, seed, iteration, horizon, member_offset,
+                      pop_shard, obs_mu, obs_nu, env_A, env_B,
+                      return_final_states=False):
+    """``es_rollout_mlp`` that also reports each member's behaviour
+    characterisation: ``bc[pop_shard][4]``, the mean over the member's 64
+    episodes of the final state ``s_horizon``, summed in a fixed order.
+
+    Returns ``(fitness, obs_stat, bc)``, or ``(fitness, obs_stat, bc,
+    final_states[pop_shard][64][4])``.  ``fitness`` and ``obs_stat`` are
+    bit-identical to ``es_rollout_mlp`` for the same arguments.
+
+    Every argument is validated before anything is launched: TypeError for
+    dtype, device or contiguity, ValueError for shape, horizon or
+    ``pop_shard``."""
+    ops = _require_ops()
+    named = (("theta", theta), ("obs_mu", obs_mu), ("obs_nu", obs_nu),
+             ("env_A", env_A), ("env_B", env_B))
+    for name, t in named:
+        _check(t, name)
+        if t.device != theta.device:
+            raise TypeError("%s is on %s, theta on %s"
+                            % (name, t.device, theta.device))
+    for name, t, want in (("theta", theta, (NPARAMS,)),
+                          ("obs_mu", obs_mu, (OBS_DIM,)),
+                          ("obs_nu", obs_nu, (OBS_DIM,)),
+                          ("env_A", env_A, (OBS_DIM, OBS_DIM)),
+                          ("env_B", env_B, (OBS_DIM,))):
+        if tuple(t.shape) != want:
+            raise ValueError("%s must be %s, got %s"
+                             % (name, list(want), tuple(t.shape)))
+    horizon, pop_shard = int(horizon), int(pop_shard)
+    member_offset = int(member_offset)
+    if horizon < 1:
+        raise ValueError("horizon must be >= 1, got %d" % horizon)
+    if pop_shard < 1:
+        raise ValueError("pop_shard must be >= 1, got %d" % pop_shard)
+    if member_offset < 0 or member_offset + pop_shard >= 2 ** 31:
+        raise ValueError("member_offset %d with pop_shard %d leaves the "
+                         "int32 member range" % (member_offset, pop_shard))
+    device = theta.device
+    fitness = torch.empty(pop_shard, dtype=torch.float32, device=device)
+    obs_stat = torch.zeros(2 * OBS_DIM + 1, dtype=torch.float32,
+                           device=device)
+    bc = torch.empty(pop_shard, BC_DIM, dtype=torch.float32, device=device)
+    final = None
+    if return_final_states:
+        final = torch.empty(pop_shard, ENVS_PER_MEMBER, OBS_DIM,
+                            dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        part = _partial_buffer(device, pop_shard * 2 * OBS_DIM)
+        ops.es_rollout_mlp_bc(
+            theta.data_ptr(), float(sigma), int(seed) & 0xFFFFFFFF,
+            int(iteration) & 0xFFFFFFFF, horizon, member_offset, pop_shard,
+            obs_mu.data_ptr(), obs_nu.data_ptr(), env_A.data_ptr(),
+            env_B.data_ptr(), fitness.data_ptr(), part.data_ptr(),
+            obs_stat.data_ptr(), bc.data_ptr(),
+            final.data_ptr() if return_final_states else 0, _stream())
+    if return_final_states:
+        return fitness, obs_stat, bc, final
+    return fitness, obs_stat, bc
+
+
+def es_eval_bc(thetas, obs_mu, obs_nu, env_A, env_B, seed, iteration,
+               horizon, return_final_states=False, return_episodes=False):
+    """``es_eval_matrix`` that also reports the behaviour characterisation
+    of every (policy, environment) cell: ``bc[K][M][4]``, the mean over the
+    cell's 64 episodes of the final state ``s_horizon``.
+
+    Arguments as ``es_eval_matrix``.  Returns ``(scores[K][M], bc)``,
+    followed by ``final_states[K][M][64][4]`` and ``episodes[K][M][64]`` if
+    asked for, in that order.  ``scores`` and ``episodes`` are bit-identical
+    to ``es_eval_matrix``; ``bc[k][m]`` is bit-identical to the ``bc`` that
+    ``es_rollout_mlp_bc`` gives for ``thetas[k]`` at ``sigma=0``.
+
+    Every argument is validated before anything is launched: TypeError for
+    dtype, device or contiguity, ValueError for shape or horizon."""
+    ops = _require_ops()
+    named = (("thetas", thetas), ("obs_mu", obs_mu), ("obs_nu", obs_nu),
+             ("env_A", env_A), ("env_B", env_B))
+    for name, t in named:
+        _check(t, name)
+        if t.device != thetas.device:
+            raise TypeError("%s is on %s, thetas on %s"
+                            % (name, t.device, thetas.device))
+    if thetas.dim() != 2 or thetas.shape[1] != NPARAMS:
+        raise ValueError("thetas must be [K, %d], got %s"
+                         % (NPARAMS, tuple(thetas.shape)))
+    K = thetas.shape[0]
+    if env_A.dim() != 3 or tuple(env_A.shape[1:]) != (OBS_DIM, OBS_DIM):
+        raise ValueError("env_A must be [M, %d, %d], got %s"
+                         % (OBS_DIM, OBS_DIM, tuple(env_A.shape)))
+    M = env_A.shape[0]
+    if K < 1 or M < 1:
+        raise ValueError("need at least one policy and one environment, "
+                         "got K = %d, M = %d" % (K, M))
+    for name, t, want in (("obs_mu", obs_mu, (K, OBS_DIM)),
+                          ("obs_nu", obs_nu, (K, OBS_DIM)),
+                          ("env_B", env_B, (M, OBS_DIM))):
+        if tuple(t.shape) != want:
+            raise ValueError("%s must be %s, got %s"
+                             % (name, list(want), tuple(t.shape)))
+    horizon = int(horizon)
+    if horizon < 1:
+        raise ValueError("horizon must be >= 1, got %d" % horizon)
+    if K * M >= 2 ** 31:
+        raise ValueError("K*M = %d exceeds the launch grid" % (K * M))
+    device = thetas.device
+    scores = torch.empty(K, M, dtype=torch.float32, device=device)
+    bc = torch.empty(K, M, BC_DIM, dtype=torch.float32, device=device)
+    final = episodes = None
+    if return_final_states:
+        final = torch.empty(K, M, ENVS_PER_MEMBER, OBS_DIM,
+                            dtype=torch.float32, device=device)
+    if return_episodes:
+        episodes = torch.empty(K, M, ENVS_PER_MEMBER, dtype=torch.float32,
+                               device=device)
+    with torch.cuda.device(device):
+        ops.es_eval_bc(
+            thetas.data_ptr(), obs_mu.data_ptr(), obs_nu.data_ptr(),
+            env_A.data_ptr(), env_B.data_ptr(), int(seed) & 0xFFFFFFFF,
+            int(iteration) & 0xFFFFFFFF, horizon, K, M, scores.data_ptr(),
+            episodes.data_ptr() if return_episodes else 0, bc.data_ptr(),
+            final.data_ptr() if return_final_states else 0, _stream())
+    out = (scores, bc)
+    if return_final_states:
+        out += (final,)
+    if return_episodes:
+        out += (episodes,)
+    return out
+
+
+def bc_knn_novelty(bc, archive, k, return_neighbours=False, out=None,
+                   out_neighbours=None):
+    """Novelty of the behaviour characterisations ``bc[N][4]`` against
+    ``archive[R][4]``: ``novelty[q]`` is the mean Euclidean distance from
+    ``bc[q]`` to its ``k`` nearest archive rows, ``1 <= k <= min(R, 16)``.
+    Duplicate archive rows count as separate neighbours.  Returns
+    ``novelty[N]``, or ``(novelty, knn_d2[N][k])`` with the ``k`` smallest
+    squared distances in ascending order.
+
+    ``out`` / ``out_neighbours`` are written instead of fresh tensors when
+    given: fp32, contiguous, on the device of ``bc``, with at least N
+    (N * k) elements, of which only the first N (N * k) are touched.
+
+    All values must be finite: with a NaN or an infinity in ``bc`` or
+    ``archive`` the novelty is unspecified.
+
+    Everything is validated before the launch: TypeError for dtype, device
+    or contiguity, ValueError for shape, an empty ``bc`` or ``archive``
+    (``R == 0``) and ``k`` outside ``[1, min(R, 16)]``."""
+    ops = _require_ops()
+    named = [("bc", bc), ("archive", archive)]
+    if out is not None:
+        named.append(("out", out))
+    if out_neighbours is not None:
+        named.append(("out_neighbours", out_neighbours))
+    for name, t in named:
+        _check(t, name)
+        if t.device != bc.device:
+            raise TypeError("%s is on %s, bc on %s"
+                            % (name, t.device, bc.device))
+    for name, t in (("bc", bc), ("archive", archive)):
+        if t.dim() != 2 or t.shape[1] != BC_DIM:
+            raise ValueError("%s must be [*, %d], got %s"
+                             % (name, BC_DIM, tuple(t.shape)))
+    N, R, k = bc.shape[0], archive.shape[0], int(k)
+    if N < 1:
+        raise ValueError("bc has no rows")
+    if R < 1:
+        raise ValueError("the archive is empty (R == 0)")
+    if k < 1 or k > BC_KNN_MAX:
+        raise ValueError("k must be in [1, %d], got %d" % (BC_KNN_MAX, k))
+    if k > R:
+        raise ValueError("k = %d exceeds the %d archive rows" % (k, R))
+    if N * k >= 2 ** 31:
+        raise ValueError("N*k = %d exceeds the launch limits" % (N * k))
+    if out is not None and out.numel() < N:
+        raise ValueError("out holds %d elements, need %d" % (out.numel(), N))
+    if out_neighbours is not None and out_neighbours.numel() < N * k:
+        raise ValueError("out_neighbours holds %d elements, need %d"
+                         % (out_neighbours.numel(), N * k))
+    device = bc.device
+    want_nb = return_neighbours or out_neighbours is not None
+    novelty = out if out is not None else torch.empty(
+        N, dtype=torch.float32, device=device)
+    knn_d2 = out_neighbours
+    if want_nb and knn_d2 is None:
+        knn_d2 = torch.empty(N, k, dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        ops.bc_knn_novelty(bc.data_ptr(), N, archive.data_ptr(), R, k,
+                           novelty.data_ptr(),
+                           knn_d2.data_ptr() if want_nb else 0, _stream())
+    if want_nb:
+        return novelty, knn_d2
+    return novelty
+
+
 def ops_available():
     return _OPS is not None

@@ -43,6 +43,9 @@ class build_ext(_build_ext):
             # translation unit of its own (register budget, see the file)
             os.path.join(ROOT, "fiber_amd", "csrc", "ops",
                          "es_pairs_kernels.hip"),
+            # novelty-search rollout + kNN kernels: the same arrangement
+            os.path.join(ROOT, "fiber_amd", "csrc", "ops",
+                         "ns_kernels.hip"),
             # PATA-EC novelty kernels: shares nothing with the rollout
             # kernels and stays out of their register allocation
             os.path.join(ROOT, "fiber_amd", "csrc", "ops",
