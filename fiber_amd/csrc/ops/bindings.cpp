@@ -62,6 +62,13 @@ extern "C" __global__ void es_eval_bc(const float*, const float*,
                                       int, float*, float*, float*, float*);
 extern "C" __global__ void bc_knn_novelty(const float*, int, const float*,
                                           int, int, float*, float*);
+// separable-NES kernels (snes_kernels.hip)
+extern "C" __global__ void es_rollout_mlp_sigma(
+    const float*, const float*, uint32_t, uint32_t, int, int, const float*,
+    const float*, const float*, const float*, float*, float*, float*);
+extern "C" __global__ void es_grad_sigma(const float*, const float*, int,
+                                         int, int, uint32_t, uint32_t, int,
+                                         float*);
 // conv policy pipeline (conv_kernels.hip)
 // PATA-EC novelty kernels (poet_kernels.hip)
 extern "C" __global__ void pata_ec_codes(const float*, int, int, int, float,
@@ -406,6 +413,65 @@ static void launch_bc_knn_novelty(uintptr_t bc, int N, uintptr_t archive,
   check(hipGetLastError(), "bc_knn_novelty launch");
 }
 
+// ---- separable-NES launchers ---------------------------------------------
+
+// launch_rollout with a device vector sigma[NPARAMS] in place of the scalar.
+static void launch_rollout_sigma(uintptr_t theta, uintptr_t sigma,
+                                 uint32_t seed, uint32_t iter, int horizon,
+                                 int member_offset, int pop_shard,
+                                 uintptr_t obs_mu, uintptr_t obs_nu,
+                                 uintptr_t env_A, uintptr_t env_B,
+                                 uintptr_t fitness, uintptr_t obs_stat_part,
+                                 uintptr_t obs_stat, uintptr_t stream) {
+  if (pop_shard <= 0) return;
+  if (horizon < 1)
+    throw std::runtime_error("es_rollout_mlp_sigma: horizon must be >= 1");
+  hipLaunchKernelGGL(es_rollout_mlp_sigma, dim3(pop_shard), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)theta,
+                     (const float*)sigma, seed, iter, horizon, member_offset,
+                     (const float*)obs_mu, (const float*)obs_nu,
+                     (const float*)env_A, (const float*)env_B,
+                     (float*)fitness, (float*)obs_stat_part,
+                     (float*)obs_stat);
+  check(hipGetLastError(), "es_rollout_mlp_sigma launch");
+  hipLaunchKernelGGL(obs_stat_reduce, dim3(2 * OBS_HOST), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)obs_stat_part,
+                     pop_shard, (float*)obs_stat);
+  check(hipGetLastError(), "obs_stat_reduce launch");
+}
+
+// The split of launch_grad with two rows per chunk: grad is [2][nparams]
+// (g_mu, g_sig), grad_part holds grad_chunks(pairs, nparams) * 2 * nparams
+// floats, and es_grad_reduce sums the partials over 2*nparams columns in
+// chunk order.
+static void launch_grad_sigma(uintptr_t wdiff, uintptr_t wsum,
+                              int pair_begin, int pair_end, uint32_t seed,
+                              uint32_t iter, int nparams,
+                              uintptr_t grad_part, uintptr_t grad,
+                              uintptr_t stream) {
+  const int jblocks = (nparams + 3) / 4;
+  const int bx = (jblocks + 255) / 256;
+  const int pairs = pair_end - pair_begin;
+  if (pairs <= 0) return;
+  if (nparams < 1 || nparams > 0x3FFFFFFF)
+    throw std::runtime_error("es_grad_sigma: bad nparams");
+  const int chunks = grad_chunks(pairs, nparams);
+  const int per_chunk = (pairs + chunks - 1) / chunks;
+  hipLaunchKernelGGL(es_grad_sigma, dim3(bx, chunks), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)wdiff,
+                     (const float*)wsum, pair_begin, pair_end, per_chunk,
+                     seed, iter, nparams,
+                     chunks == 1 ? (float*)grad : (float*)grad_part);
+  check(hipGetLastError(), "es_grad_sigma launch");
+  if (chunks > 1) {
+    hipLaunchKernelGGL(es_grad_reduce, dim3((2 * nparams + 255) / 256),
+                       dim3(256), 0, (hipStream_t)stream,
+                       (const float*)grad_part, chunks, 2 * nparams,
+                       (float*)grad);
+    check(hipGetLastError(), "es_grad_reduce launch");
+  }
+}
+
 // ---- conv pipeline launchers ---------------------------------------------
 
 static void launch_perturb(uintptr_t theta, int nparams, int np_pad,
@@ -588,6 +654,16 @@ PYBIND11_MODULE(_ops, m) {
   m.def("bc_knn_novelty", &launch_bc_knn_novelty, py::arg("bc"),
         py::arg("N"), py::arg("archive"), py::arg("R"), py::arg("k"),
         py::arg("novelty"), py::arg("knn_d2"), py::arg("stream"));
+  m.def("es_rollout_mlp_sigma", &launch_rollout_sigma, py::arg("theta"),
+        py::arg("sigma"), py::arg("seed"), py::arg("iter"),
+        py::arg("horizon"), py::arg("member_offset"), py::arg("pop_shard"),
+        py::arg("obs_mu"), py::arg("obs_nu"), py::arg("env_A"),
+        py::arg("env_B"), py::arg("fitness"), py::arg("obs_stat_part"),
+        py::arg("obs_stat"), py::arg("stream"));
+  m.def("es_grad_sigma", &launch_grad_sigma, py::arg("wdiff"),
+        py::arg("wsum"), py::arg("pair_begin"), py::arg("pair_end"),
+        py::arg("seed"), py::arg("iter"), py::arg("nparams"),
+        py::arg("grad_part"), py::arg("grad"), py::arg("stream"));
   m.def("pata_ec_codes", &launch_pata_ec_codes, py::arg("scores"),
         py::arg("K"), py::arg("M"), py::arg("Kpad"), py::arg("lo"),
         py::arg("hi"), py::arg("codes"), py::arg("stream"));

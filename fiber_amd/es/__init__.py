@@ -7,6 +7,7 @@ from .engine import (  # noqa: F401
 )
 from .novelty import NoveltyConfig, NoveltyESEngine  # noqa: F401
 from .population import ESPopulation  # noqa: F401
+from .snes import SNESConfig, SNESEngine  # noqa: F401
 from .poet import (  # noqa: F401
     apply_transfers,
     minimal_criterion,

@@ -709,5 +709,131 @@ def bc_knn_novelty(bc, archive, k, return_neighbours=False, out=None,
     return novelty
 
 
+# ---------------------------------------------------------------------------
+# Separable NES (snes_kernels.hip): the rollout with a step size per
+# parameter, and the gradient with the second-moment row that adapts it.
+# ---------------------------------------------------------------------------
+
+
+def es_rollout_mlp_sigma(theta, sigma_vec, seed, iteration, horizon,
+                         member_offset, pop_shard, obs_mu, obs_nu, env_A,
+                         env_B):
+    """``es_rollout_mlp`` with a step size per parameter: member ``m``
+    evaluates ``theta[j] + s_j * z[j]`` with ``s_j = sigma_vec[j]`` for even
+    ``m`` and ``-sigma_vec[j]`` for odd ``m``, ``z`` the draws of pair
+    ``m // 2``.  Returns ``(fitness[pop_shard], obs_stat[9])``; for
+    ``sigma_vec = full(s)`` both are bit-identical to ``es_rollout_mlp`` at
+    ``sigma = s``.
+
+    ``sigma_vec`` is fp32 ``[NPARAMS]`` on the device of ``theta``.  Its
+    values must be finite and >= 0; this is not checked on the device, and a
+    NaN, an infinity or a negative entry gives an unspecified policy.
+
+    Every argument is validated before anything is launched: TypeError for
+    dtype, device or contiguity, ValueError for shape, ``horizon < 1``,
+    ``pop_shard < 1`` or a member range that leaves int32."""
+    ops = _require_ops()
+    if not torch.is_tensor(sigma_vec):
+        raise TypeError("sigma_vec must be a tensor [%d], got %s (for a "
+                        "scalar sigma use es_rollout_mlp)"
+                        % (NPARAMS, type(sigma_vec).__name__))
+    named = (("theta", theta), ("sigma_vec", sigma_vec), ("obs_mu", obs_mu),
+             ("obs_nu", obs_nu), ("env_A", env_A), ("env_B", env_B))
+    for name, t in named:
+        _check(t, name)
+        if t.device != theta.device:
+            raise TypeError("%s is on %s, theta on %s"
+                            % (name, t.device, theta.device))
+    for name, t, want in (("theta", theta, (NPARAMS,)),
+                          ("sigma_vec", sigma_vec, (NPARAMS,)),
+                          ("obs_mu", obs_mu, (OBS_DIM,)),
+                          ("obs_nu", obs_nu, (OBS_DIM,)),
+                          ("env_A", env_A, (OBS_DIM, OBS_DIM)),
+                          ("env_B", env_B, (OBS_DIM,))):
+        if tuple(t.shape) != want:
+            raise ValueError("%s must be %s, got %s"
+                             % (name, list(want), tuple(t.shape)))
+    horizon, pop_shard = int(horizon), int(pop_shard)
+    member_offset = int(member_offset)
+    if horizon < 1:
+        raise ValueError("horizon must be >= 1, got %d" % horizon)
+    if pop_shard < 1:
+        raise ValueError("pop_shard must be >= 1, got %d" % pop_shard)
+    if member_offset < 0 or member_offset + pop_shard >= 2 ** 31:
+        raise ValueError("member_offset %d with pop_shard %d leaves the "
+                         "int32 member range" % (member_offset, pop_shard))
+    device = theta.device
+    fitness = torch.empty(pop_shard, dtype=torch.float32, device=device)
+    obs_stat = torch.zeros(2 * OBS_DIM + 1, dtype=torch.float32,
+                           device=device)
+    with torch.cuda.device(device):
+        part = _partial_buffer(device, pop_shard * 2 * OBS_DIM)
+        ops.es_rollout_mlp_sigma(
+            theta.data_ptr(), sigma_vec.data_ptr(), int(seed) & 0xFFFFFFFF,
+            int(iteration) & 0xFFFFFFFF, horizon, member_offset, pop_shard,
+            obs_mu.data_ptr(), obs_nu.data_ptr(), env_A.data_ptr(),
+            env_B.data_ptr(), fitness.data_ptr(), part.data_ptr(),
+            obs_stat.data_ptr(), _stream())
+    return fitness, obs_stat
+
+
+def es_grad_sigma(wdiff, wsum, pair_begin, pair_end, seed, iteration, device,
+                  nparams=None):
+    """Both rows of the separable-NES gradient over the pairs ``pair_begin
+    <= k < pair_end``, from one regeneration of each draw ``z_k``:
+
+      ``g_mu[j]  = sum_k wdiff[k] * z_k[j]``
+      ``g_sig[j] = sum_k wsum[k] * (z_k[j]**2 - 1)``
+
+    ``wdiff`` and ``wsum`` are fp32 vectors of equal length, indexed by the
+    pair number like ``es_grad``'s ``wpair``; nothing outside the range is
+    read.  Returns ``(g_mu, g_sig)``, the two rows of one ``[2, nparams]``
+    tensor.  ``g_mu`` is bit-identical to ``es_grad(wdiff, ...)``; both rows
+    are sums in a fixed order, so two calls give the same bits.
+
+    Everything is validated before the launch: TypeError for dtype, device
+    or contiguity, ValueError for shape, a bad pair range, ``nparams < 1``,
+    and ``wdiff`` / ``wsum`` of different length or shorter than
+    ``pair_end``."""
+    ops = _require_ops()
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise TypeError("device must be a CUDA (ROCm) device, got %s" % dev)
+    for name, t in (("wdiff", wdiff), ("wsum", wsum)):
+        _check(t, name)
+        if t.device != wdiff.device or (dev.index is not None
+                                        and t.device != dev):
+            raise TypeError("%s is on %s, expected %s"
+                            % (name, t.device, device))
+    if nparams is None:
+        nparams = NPARAMS
+    nparams = int(nparams)
+    pair_begin, pair_end = int(pair_begin), int(pair_end)
+    for name, t in (("wdiff", wdiff), ("wsum", wsum)):
+        if t.dim() != 1:
+            raise ValueError("%s must be 1-d, got %s"
+                             % (name, tuple(t.shape)))
+    if wdiff.numel() != wsum.numel():
+        raise ValueError("wdiff holds %d weights, wsum %d"
+                         % (wdiff.numel(), wsum.numel()))
+    if pair_begin < 0 or pair_end < pair_begin or pair_end >= 2 ** 30:
+        raise ValueError("bad pair range [%d, %d)" % (pair_begin, pair_end))
+    if wdiff.numel() < pair_end:
+        raise ValueError("the weights hold %d pairs, pair_end is %d"
+                         % (wdiff.numel(), pair_end))
+    if nparams < 1 or nparams >= 2 ** 30:
+        raise ValueError("nparams must be in [1, 2**30), got %d" % nparams)
+    device = wdiff.device
+    grad = torch.zeros(2, nparams, dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        chunks = ops.es_grad_chunks(pair_end - pair_begin, nparams)
+        part = _partial_buffer(device, chunks * 2 * nparams)
+        ops.es_grad_sigma(wdiff.data_ptr(), wsum.data_ptr(), pair_begin,
+                          pair_end, int(seed) & 0xFFFFFFFF,
+                          int(iteration) & 0xFFFFFFFF, nparams,
+                          part.data_ptr(), grad.data_ptr(), _stream())
+    return grad[0], grad[1]
+
+
 def ops_available():
     return _OPS is not None

@@ -46,6 +46,9 @@ class build_ext(_build_ext):
             # novelty-search rollout + kNN kernels: the same arrangement
             os.path.join(ROOT, "fiber_amd", "csrc", "ops",
                          "ns_kernels.hip"),
+            # separable-NES rollout + two-row gradient: the same arrangement
+            os.path.join(ROOT, "fiber_amd", "csrc", "ops",
+                         "snes_kernels.hip"),
             # PATA-EC novelty kernels: shares nothing with the rollout
             # kernels and stays out of their register allocation
             os.path.join(ROOT, "fiber_amd", "csrc", "ops",
