@@ -69,6 +69,19 @@ extern "C" __global__ void es_rollout_mlp_sigma(
 extern "C" __global__ void es_grad_sigma(const float*, const float*, int,
                                          int, int, uint32_t, uint32_t, int,
                                          float*);
+// Deep GA kernels (ga_kernels.hip)
+extern "C" __global__ void ga_parents(uint32_t, uint32_t, int, int, uint32_t,
+                                      int*, int*);
+extern "C" __global__ void ga_rollout_mlp(
+    const float*, const int*, const int*, float, uint32_t, uint32_t, int,
+    const float*, const float*, const float*, const float*, float*, float*,
+    float*);
+extern "C" __global__ void ga_truncate(const float*, int, int, int*);
+extern "C" __global__ void ga_survivors(const float*, const int*, const int*,
+                                        const int*, float, uint32_t, uint32_t,
+                                        float*);
+extern "C" __global__ void ga_decode(const float*, const int*, int, float,
+                                     uint32_t, float*);
 // conv policy pipeline (conv_kernels.hip)
 // PATA-EC novelty kernels (poet_kernels.hip)
 extern "C" __global__ void pata_ec_codes(const float*, int, int, int, float,
@@ -472,6 +485,88 @@ static void launch_grad_sigma(uintptr_t wdiff, uintptr_t wsum,
   }
 }
 
+// ---- Deep GA launchers ------------------------------------------------------
+// ga_truncate counts over all n per thread and stops at 65536 members;
+// ga_survivors and ga_decode carry the row in grid.y.
+#define GA_TRUNCATE_MAX_HOST 65536
+#define GA_ROWS_MAX_HOST 65535
+
+static void launch_ga_parents(uint32_t seed, uint32_t gen, int pop,
+                              int n_elite, int T_cur, uintptr_t parent_idx,
+                              uintptr_t slot, uintptr_t stream) {
+  if (pop < 1 || T_cur < 1 || n_elite < 0 || n_elite > T_cur)
+    throw std::runtime_error("ga_parents: bad pop, n_elite or T_cur");
+  hipLaunchKernelGGL(ga_parents, dim3((unsigned)((pop + 255) / 256)),
+                     dim3(256), 0, (hipStream_t)stream, seed, gen, pop,
+                     n_elite, (uint32_t)T_cur, (int*)parent_idx, (int*)slot);
+  check(hipGetLastError(), "ga_parents launch");
+}
+
+// launch_rollout with a parent row and a draw per member.
+static void launch_ga_rollout(uintptr_t parents, uintptr_t parent_idx,
+                              uintptr_t slot, double sigma, uint32_t seed,
+                              uint32_t gen, int horizon, int pop,
+                              uintptr_t obs_mu, uintptr_t obs_nu,
+                              uintptr_t env_A, uintptr_t env_B,
+                              uintptr_t fitness, uintptr_t obs_stat_part,
+                              uintptr_t obs_stat, uintptr_t stream) {
+  if (pop < 1) throw std::runtime_error("ga_rollout_mlp: pop must be >= 1");
+  if (horizon < 1)
+    throw std::runtime_error("ga_rollout_mlp: horizon must be >= 1");
+  hipLaunchKernelGGL(ga_rollout_mlp, dim3(pop), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)parents,
+                     (const int*)parent_idx, (const int*)slot, (float)sigma,
+                     seed, gen, horizon, (const float*)obs_mu,
+                     (const float*)obs_nu, (const float*)env_A,
+                     (const float*)env_B, (float*)fitness,
+                     (float*)obs_stat_part, (float*)obs_stat);
+  check(hipGetLastError(), "ga_rollout_mlp launch");
+  hipLaunchKernelGGL(obs_stat_reduce, dim3(2 * OBS_HOST), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)obs_stat_part, pop,
+                     (float*)obs_stat);
+  check(hipGetLastError(), "obs_stat_reduce launch");
+}
+
+static void launch_ga_truncate(uintptr_t f, int n, int T, uintptr_t order,
+                               uintptr_t stream) {
+  if (n < 2 || n > GA_TRUNCATE_MAX_HOST || T < 1 || T > n)
+    throw std::runtime_error("ga_truncate: bad n or T");
+  hipLaunchKernelGGL(ga_truncate, dim3((unsigned)((n + 255) / 256)),
+                     dim3(256), 0, (hipStream_t)stream, (const float*)f, n,
+                     T, (int*)order);
+  check(hipGetLastError(), "ga_truncate launch");
+}
+
+static void launch_ga_survivors(uintptr_t parents, uintptr_t parent_idx,
+                                uintptr_t slot, uintptr_t order, int T,
+                                double sigma, uint32_t seed, uint32_t gen,
+                                uintptr_t new_parents, uintptr_t stream) {
+  if (T < 1 || T > GA_ROWS_MAX_HOST)
+    throw std::runtime_error("ga_survivors: bad T");
+  if (parents == new_parents)
+    throw std::runtime_error("ga_survivors: new_parents aliases parents");
+  const int bx = ((NPARAMS_HOST + 3) / 4 + 255) / 256;
+  hipLaunchKernelGGL(ga_survivors, dim3(bx, T), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)parents,
+                     (const int*)parent_idx, (const int*)slot,
+                     (const int*)order, (float)sigma, seed, gen,
+                     (float*)new_parents);
+  check(hipGetLastError(), "ga_survivors launch");
+}
+
+static void launch_ga_decode(uintptr_t theta0, uintptr_t lineage, int N,
+                             int G, double sigma, uint32_t seed,
+                             uintptr_t thetas, uintptr_t stream) {
+  if (N < 1 || N > GA_ROWS_MAX_HOST || G < 0)
+    throw std::runtime_error("ga_decode: bad N or G");
+  const int bx = ((NPARAMS_HOST + 3) / 4 + 255) / 256;
+  hipLaunchKernelGGL(ga_decode, dim3(bx, N), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)theta0,
+                     (const int*)lineage, G, (float)sigma, seed,
+                     (float*)thetas);
+  check(hipGetLastError(), "ga_decode launch");
+}
+
 // ---- conv pipeline launchers ---------------------------------------------
 
 static void launch_perturb(uintptr_t theta, int nparams, int np_pad,
@@ -664,6 +759,26 @@ PYBIND11_MODULE(_ops, m) {
         py::arg("wsum"), py::arg("pair_begin"), py::arg("pair_end"),
         py::arg("seed"), py::arg("iter"), py::arg("nparams"),
         py::arg("grad_part"), py::arg("grad"), py::arg("stream"));
+  m.attr("GA_TRUNCATE_MAX") = GA_TRUNCATE_MAX_HOST;
+  m.attr("GA_ROWS_MAX") = GA_ROWS_MAX_HOST;
+  m.def("ga_parents", &launch_ga_parents, py::arg("seed"), py::arg("gen"),
+        py::arg("pop"), py::arg("n_elite"), py::arg("T_cur"),
+        py::arg("parent_idx"), py::arg("slot"), py::arg("stream"));
+  m.def("ga_rollout_mlp", &launch_ga_rollout, py::arg("parents"),
+        py::arg("parent_idx"), py::arg("slot"), py::arg("sigma"),
+        py::arg("seed"), py::arg("gen"), py::arg("horizon"), py::arg("pop"),
+        py::arg("obs_mu"), py::arg("obs_nu"), py::arg("env_A"),
+        py::arg("env_B"), py::arg("fitness"), py::arg("obs_stat_part"),
+        py::arg("obs_stat"), py::arg("stream"));
+  m.def("ga_truncate", &launch_ga_truncate, py::arg("f"), py::arg("n"),
+        py::arg("T"), py::arg("order"), py::arg("stream"));
+  m.def("ga_survivors", &launch_ga_survivors, py::arg("parents"),
+        py::arg("parent_idx"), py::arg("slot"), py::arg("order"),
+        py::arg("T"), py::arg("sigma"), py::arg("seed"), py::arg("gen"),
+        py::arg("new_parents"), py::arg("stream"));
+  m.def("ga_decode", &launch_ga_decode, py::arg("theta0"),
+        py::arg("lineage"), py::arg("N"), py::arg("G"), py::arg("sigma"),
+        py::arg("seed"), py::arg("thetas"), py::arg("stream"));
   m.def("pata_ec_codes", &launch_pata_ec_codes, py::arg("scores"),
         py::arg("K"), py::arg("M"), py::arg("Kpad"), py::arg("lo"),
         py::arg("hi"), py::arg("codes"), py::arg("stream"));

@@ -835,5 +835,258 @@ def es_grad_sigma(wdiff, wsum, pair_begin, pair_end, seed, iteration, device,
     return grad[0], grad[1]
 
 
+# ---------------------------------------------------------------------------
+# Deep GA (ga_kernels.hip): a population of mutated copies of T parents,
+# truncation selection with an exact tie order, and weights rebuilt from
+# chains of mutation seeds.  The mutation of child slot i in generation g is
+# the draw es_rollout_mlp uses for pair i at iteration g.
+# ---------------------------------------------------------------------------
+
+GA_TRUNCATE_MAX = _OPS.GA_TRUNCATE_MAX if _OPS else 65536  # members ranked
+GA_ROWS_MAX = _OPS.GA_ROWS_MAX if _OPS else 65535  # rows that ride grid.y
+
+
+def _check_ga_on(named, anchor_name, anchor):
+    """dtype / device / contiguity of every (name, tensor, dtype), all on
+    the device of ``anchor``."""
+    for name, t, dtype in named:
+        if not torch.is_tensor(t):
+            raise TypeError("%s must be a tensor, got %s"
+                            % (name, type(t).__name__))
+        _check(t, name, dtype=dtype)
+        if t.device != anchor.device:
+            raise TypeError("%s is on %s, %s on %s"
+                            % (name, t.device, anchor_name, anchor.device))
+
+
+def _check_ga_sigma(sigma):
+    sigma = float(sigma)
+    if not 0.0 <= sigma < float("inf"):  # also refuses a NaN
+        raise ValueError("sigma must be finite and >= 0, got %r" % sigma)
+    return sigma
+
+
+def ga_parents(seed, generation, pop, n_elite, T_cur, device):
+    """Who mutates whom in one generation: int32 ``(parent_idx[pop],
+    slot[pop])``.  Member ``m < n_elite`` is survivor ``m`` unmutated
+    (``parent_idx = m``, ``slot = -1``); member ``m >= n_elite`` has ``slot
+    = m`` and ``parent_idx = (u * T_cur) >> 32`` with ``u`` the first word
+    of one Philox draw keyed by ``(seed, generation, m)``.  Integer
+    arithmetic only: ``ga_oracle.parents_exact`` reproduces it exactly.
+
+    TypeError for a device that is not a GPU; ValueError unless ``1 <= pop <
+    2**31``, ``1 <= T_cur < 2**31`` and ``0 <= n_elite <= min(T_cur,
+    pop)``."""
+    ops = _require_ops()
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise TypeError("device must be a CUDA (ROCm) device, got %s"
+                        % device)
+    pop, n_elite, T_cur = int(pop), int(n_elite), int(T_cur)
+    if pop < 1 or pop >= 2 ** 31:
+        raise ValueError("pop must be in [1, 2**31), got %d" % pop)
+    if T_cur < 1 or T_cur >= 2 ** 31:
+        raise ValueError("T_cur must be in [1, 2**31), got %d" % T_cur)
+    if n_elite < 0 or n_elite > T_cur or n_elite > pop:
+        raise ValueError("n_elite must be in [0, min(T_cur, pop)] = [0, %d], "
+                         "got %d" % (min(T_cur, pop), n_elite))
+    parent_idx = torch.empty(pop, dtype=torch.int32, device=device)
+    slot = torch.empty(pop, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        ops.ga_parents(int(seed) & 0xFFFFFFFF, int(generation) & 0xFFFFFFFF,
+                       pop, n_elite, T_cur, parent_idx.data_ptr(),
+                       slot.data_ptr(), _stream())
+    return parent_idx, slot
+
+
+def ga_rollout_mlp(parents, parent_idx, slot, sigma, seed, generation,
+                   horizon, obs_mu, obs_nu, env_A, env_B):
+    """Roll out a population in which member ``m`` is row ``parent_idx[m]``
+    of ``parents[T][NPARAMS]``, as it is for ``slot[m] < 0`` and otherwise
+    mutated: ``parent[j] + sigma * z[j]`` in one fma, ``z`` the draw of
+    child slot ``slot[m]`` in this generation.  Returns ``(fitness[pop],
+    obs_stat[9])`` like ``es_rollout_mlp``.  A mutated member carries the
+    bits of that kernel's member ``2 * slot`` for the same parent, an
+    unmutated one those of ``es_eval_matrix`` for its row.
+
+    The caller's contract, which cannot be checked without a host sync:
+    every ``parent_idx[m]`` lies in ``[0, T)`` (another value reads outside
+    ``parents``) and every ``slot[m]`` is below ``2**31``.  ``ga_parents``
+    writes such values.
+
+    Everything else is validated before anything is launched: TypeError for
+    dtype, device or contiguity, ValueError for shapes, ``horizon < 1`` or a
+    sigma that is negative or not finite."""
+    ops = _require_ops()
+    _check_ga_on(
+        (("parents", parents, torch.float32),
+         ("parent_idx", parent_idx, torch.int32),
+         ("slot", slot, torch.int32), ("obs_mu", obs_mu, torch.float32),
+         ("obs_nu", obs_nu, torch.float32), ("env_A", env_A, torch.float32),
+         ("env_B", env_B, torch.float32)), "parents", parents)
+    if parents.dim() != 2 or parents.shape[1] != NPARAMS \
+            or parents.shape[0] < 1:
+        raise ValueError("parents must be [T, %d] with T >= 1, got %s"
+                         % (NPARAMS, tuple(parents.shape)))
+    if parent_idx.dim() != 1 or parent_idx.numel() < 1:
+        raise ValueError("parent_idx must be [pop] with pop >= 1, got %s"
+                         % (tuple(parent_idx.shape),))
+    pop = parent_idx.numel()
+    for name, t, want in (("slot", slot, (pop,)),
+                          ("obs_mu", obs_mu, (OBS_DIM,)),
+                          ("obs_nu", obs_nu, (OBS_DIM,)),
+                          ("env_A", env_A, (OBS_DIM, OBS_DIM)),
+                          ("env_B", env_B, (OBS_DIM,))):
+        if tuple(t.shape) != want:
+            raise ValueError("%s must be %s, got %s"
+                             % (name, list(want), tuple(t.shape)))
+    horizon = int(horizon)
+    if horizon < 1:
+        raise ValueError("horizon must be >= 1, got %d" % horizon)
+    if pop >= 2 ** 31:
+        raise ValueError("pop = %d exceeds the launch grid" % pop)
+    sigma = _check_ga_sigma(sigma)
+    device = parents.device
+    fitness = torch.empty(pop, dtype=torch.float32, device=device)
+    obs_stat = torch.zeros(2 * OBS_DIM + 1, dtype=torch.float32,
+                           device=device)
+    with torch.cuda.device(device):
+        part = _partial_buffer(device, pop * 2 * OBS_DIM)
+        ops.ga_rollout_mlp(
+            parents.data_ptr(), parent_idx.data_ptr(), slot.data_ptr(),
+            sigma, int(seed) & 0xFFFFFFFF, int(generation) & 0xFFFFFFFF,
+            horizon, pop, obs_mu.data_ptr(), obs_nu.data_ptr(),
+            env_A.data_ptr(), env_B.data_ptr(), fitness.data_ptr(),
+            part.data_ptr(), obs_stat.data_ptr(), _stream())
+    return fitness, obs_stat
+
+
+def ga_truncate(fitness, T):
+    """Truncation selection: int32 ``order[T]``, ``order[r]`` the index of
+    the member of descending rank ``r``, where ``rank(i) = #{j : f[j] > f[i]
+    or (f[j] == f[i] and j < i)}``.  A NaN ranks below every number, NaNs
+    among themselves by index, and ``-0 == +0``.  Exact: comparisons only.
+
+    TypeError for dtype, device or contiguity; ValueError unless ``fitness``
+    is 1-d with ``2 <= n <= 65536`` and ``1 <= T <= n``."""
+    ops = _require_ops()
+    _check_ga_on((("fitness", fitness, torch.float32),), "fitness", fitness)
+    if fitness.dim() != 1:
+        raise ValueError("fitness must be 1-d, got %s"
+                         % (tuple(fitness.shape),))
+    n, T = fitness.numel(), int(T)
+    if n < 2 or n > GA_TRUNCATE_MAX:
+        raise ValueError("n must be in [2, %d], got %d"
+                         % (GA_TRUNCATE_MAX, n))
+    if T < 1 or T > n:
+        raise ValueError("T must be in [1, n] = [1, %d], got %d" % (n, T))
+    order = torch.empty(T, dtype=torch.int32, device=fitness.device)
+    with torch.cuda.device(fitness.device):
+        ops.ga_truncate(fitness.data_ptr(), n, T, order.data_ptr(),
+                        _stream())
+    return order
+
+
+def ga_survivors(parents, parent_idx, slot, order, sigma, seed, generation,
+                 out=None):
+    """The weights the survivors were evaluated with: row ``t`` of
+    ``new_parents[T][NPARAMS]`` is member ``order[t]`` of the launch that
+    ``ga_rollout_mlp`` made from the same ``(parents, parent_idx, slot,
+    sigma, seed, generation)``, its parent row as it is for ``slot < 0`` and
+    the same multiply-add otherwise.  Out of place: ``out``, if given, is
+    fp32 ``[T][NPARAMS]`` storage that shares no memory with ``parents``.
+
+    The caller's contract: ``order`` values in ``[0, pop)``, ``parent_idx``
+    values in ``[0, T_cur)``, as ``ga_truncate`` and ``ga_parents`` write
+    them.  TypeError for dtype, device or contiguity, ValueError for shapes,
+    ``T`` outside ``[1, 65535]``, an ``out`` that overlaps ``parents`` or a
+    bad sigma."""
+    ops = _require_ops()
+    named = [("parents", parents, torch.float32),
+             ("parent_idx", parent_idx, torch.int32),
+             ("slot", slot, torch.int32), ("order", order, torch.int32)]
+    if out is not None:
+        named.append(("out", out, torch.float32))
+    _check_ga_on(named, "parents", parents)
+    if parents.dim() != 2 or parents.shape[1] != NPARAMS \
+            or parents.shape[0] < 1:
+        raise ValueError("parents must be [T_cur, %d] with T_cur >= 1, got %s"
+                         % (NPARAMS, tuple(parents.shape)))
+    if parent_idx.dim() != 1 or parent_idx.numel() < 1:
+        raise ValueError("parent_idx must be [pop] with pop >= 1, got %s"
+                         % (tuple(parent_idx.shape),))
+    pop = parent_idx.numel()
+    if tuple(slot.shape) != (pop,):
+        raise ValueError("slot must be [%d], got %s"
+                         % (pop, tuple(slot.shape)))
+    if order.dim() != 1:
+        raise ValueError("order must be 1-d, got %s" % (tuple(order.shape),))
+    T = order.numel()
+    if T < 1 or T > GA_ROWS_MAX or T > pop:
+        raise ValueError("T must be in [1, min(pop, %d)], got %d"
+                         % (GA_ROWS_MAX, T))
+    sigma = _check_ga_sigma(sigma)
+    device = parents.device
+    if out is None:
+        out = torch.empty(T, NPARAMS, dtype=torch.float32, device=device)
+    else:
+        if tuple(out.shape) != (T, NPARAMS):
+            raise ValueError("out must be [%d, %d], got %s"
+                             % (T, NPARAMS, tuple(out.shape)))
+        lo, hi = out.data_ptr(), out.data_ptr() + out.numel() * 4
+        plo = parents.data_ptr()
+        phi = plo + parents.numel() * 4
+        if lo < phi and plo < hi:
+            raise ValueError("out overlaps parents: ga_survivors is out of "
+                             "place")
+    with torch.cuda.device(device):
+        ops.ga_survivors(parents.data_ptr(), parent_idx.data_ptr(),
+                         slot.data_ptr(), order.data_ptr(), T, sigma,
+                         int(seed) & 0xFFFFFFFF,
+                         int(generation) & 0xFFFFFFFF, out.data_ptr(),
+                         _stream())
+    return out
+
+
+def ga_decode(theta0, lineage, sigma, seed, out=None):
+    """Weights from seed chains.  ``lineage`` is int32 ``[N][G]``: column
+    ``c`` of a row holds the child slot whose draw was applied in generation
+    ``c``, or a negative value for a generation the genome passed through
+    unmutated.  ``thetas[n] = theta0``, then for ``c = 0 .. G-1`` in order
+    ``acc = fma(sigma, z(seed, c, lineage[n][c]), acc)``: the fold
+    ``ga_survivors`` performs generation by generation, so the result
+    carries the bits of the parents it materialised.  ``G = 0`` gives copies
+    of ``theta0``.  ``out``, if given, is fp32 ``[N][NPARAMS]``.
+
+    TypeError for dtype, device or contiguity, ValueError for shapes, ``N``
+    outside ``[1, 65535]`` or a bad sigma."""
+    ops = _require_ops()
+    named = [("theta0", theta0, torch.float32),
+             ("lineage", lineage, torch.int32)]
+    if out is not None:
+        named.append(("out", out, torch.float32))
+    _check_ga_on(named, "theta0", theta0)
+    if tuple(theta0.shape) != (NPARAMS,):
+        raise ValueError("theta0 must be [%d], got %s"
+                         % (NPARAMS, tuple(theta0.shape)))
+    if lineage.dim() != 2:
+        raise ValueError("lineage must be [N, G], got %s"
+                         % (tuple(lineage.shape),))
+    N, G = lineage.shape
+    if N < 1 or N > GA_ROWS_MAX:
+        raise ValueError("N must be in [1, %d], got %d" % (GA_ROWS_MAX, N))
+    sigma = _check_ga_sigma(sigma)
+    device = theta0.device
+    if out is None:
+        out = torch.empty(N, NPARAMS, dtype=torch.float32, device=device)
+    elif tuple(out.shape) != (N, NPARAMS):
+        raise ValueError("out must be [%d, %d], got %s"
+                         % (N, NPARAMS, tuple(out.shape)))
+    with torch.cuda.device(device):
+        ops.ga_decode(theta0.data_ptr(), lineage.data_ptr(), N, G, sigma,
+                      int(seed) & 0xFFFFFFFF, out.data_ptr(), _stream())
+    return out
+
+
 def ops_available():
     return _OPS is not None

@@ -49,6 +49,10 @@ class build_ext(_build_ext):
             # separable-NES rollout + two-row gradient: the same arrangement
             os.path.join(ROOT, "fiber_amd", "csrc", "ops",
                          "snes_kernels.hip"),
+            # Deep GA rollout, truncation and seed-chain decode: the same
+            # arrangement
+            os.path.join(ROOT, "fiber_amd", "csrc", "ops",
+                         "ga_kernels.hip"),
             # PATA-EC novelty kernels: shares nothing with the rollout
             # kernels and stays out of their register allocation
             os.path.join(ROOT, "fiber_amd", "csrc", "ops",
