@@ -13,6 +13,8 @@
 #include <stdexcept>
 #include <string>
 
+#include "me_grid.h"
+
 namespace py = pybind11;
 
 #define NPARAMS_HOST 4610
@@ -82,6 +84,19 @@ extern "C" __global__ void ga_survivors(const float*, const int*, const int*,
                                         float*);
 extern "C" __global__ void ga_decode(const float*, const int*, int, float,
                                      uint32_t, float*);
+// MAP-Elites kernels (me_kernels.hip)
+extern "C" __global__ void me_parents(uint32_t, uint32_t, int, const int*,
+                                      const int*, int, int*, int*);
+extern "C" __global__ void ga_rollout_mlp_bc(
+    const float*, const int*, const int*, float, uint32_t, uint32_t, int,
+    const float*, const float*, const float*, const float*, float*, float*,
+    float*, float*, float*);
+extern "C" __global__ void me_assign(const float*, const float*, int, MeGrid,
+                                     int*, unsigned long long*);
+extern "C" __global__ void me_commit(const float*, const float*, int, int,
+                                     const unsigned long long*, float*,
+                                     float*, int*, int*, int*);
+extern "C" __global__ void me_compact(const int*, int, int*, int*);
 // conv policy pipeline (conv_kernels.hip)
 // PATA-EC novelty kernels (poet_kernels.hip)
 extern "C" __global__ void pata_ec_codes(const float*, int, int, int, float,
@@ -567,6 +582,102 @@ static void launch_ga_decode(uintptr_t theta0, uintptr_t lineage, int N,
   check(hipGetLastError(), "ga_decode launch");
 }
 
+// ---- MAP-Elites launchers ---------------------------------------------------
+// The archive's rows ride grid.y of ga_survivors and ga_decode with the root
+// row behind them, so C + 1 <= GA_ROWS_MAX.
+#define ME_CELLS_MAX_HOST (GA_ROWS_MAX_HOST - 1)
+
+static void launch_me_parents(uint32_t seed, uint32_t gen, int pop,
+                              uintptr_t filled_idx, uintptr_t n_filled,
+                              int root_row, uintptr_t parent_idx,
+                              uintptr_t slot, uintptr_t stream) {
+  if (pop < 1 || root_row < 0)
+    throw std::runtime_error("me_parents: bad pop or root_row");
+  hipLaunchKernelGGL(me_parents, dim3((unsigned)((pop + 255) / 256)),
+                     dim3(256), 0, (hipStream_t)stream, seed, gen, pop,
+                     (const int*)filled_idx, (const int*)n_filled, root_row,
+                     (int*)parent_idx, (int*)slot);
+  check(hipGetLastError(), "me_parents launch");
+}
+
+// launch_ga_rollout with a BC per member.
+static void launch_ga_rollout_bc(uintptr_t parents, uintptr_t parent_idx,
+                                 uintptr_t slot, double sigma, uint32_t seed,
+                                 uint32_t gen, int horizon, int pop,
+                                 uintptr_t obs_mu, uintptr_t obs_nu,
+                                 uintptr_t env_A, uintptr_t env_B,
+                                 uintptr_t fitness, uintptr_t obs_stat_part,
+                                 uintptr_t obs_stat, uintptr_t bc,
+                                 uintptr_t final_states, uintptr_t stream) {
+  if (pop < 1)
+    throw std::runtime_error("ga_rollout_mlp_bc: pop must be >= 1");
+  if (horizon < 1)
+    throw std::runtime_error("ga_rollout_mlp_bc: horizon must be >= 1");
+  hipLaunchKernelGGL(ga_rollout_mlp_bc, dim3(pop), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)parents,
+                     (const int*)parent_idx, (const int*)slot, (float)sigma,
+                     seed, gen, horizon, (const float*)obs_mu,
+                     (const float*)obs_nu, (const float*)env_A,
+                     (const float*)env_B, (float*)fitness,
+                     (float*)obs_stat_part, (float*)obs_stat, (float*)bc,
+                     (float*)final_states);
+  check(hipGetLastError(), "ga_rollout_mlp_bc launch");
+  hipLaunchKernelGGL(obs_stat_reduce, dim3(2 * OBS_HOST), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)obs_stat_part, pop,
+                     (float*)obs_stat);
+  check(hipGetLastError(), "obs_stat_reduce launch");
+}
+
+// best[C] is 64-bit scratch, zeroed here on the stream before me_assign.
+static void launch_me_insert(uintptr_t fitness, uintptr_t bc, int pop,
+                             py::tuple bins, py::tuple lo, py::tuple inv,
+                             uintptr_t arch_fitness, uintptr_t arch_bc,
+                             uintptr_t arch_filled, uintptr_t best,
+                             uintptr_t cell, uintptr_t winner,
+                             uintptr_t order, uintptr_t stream) {
+  if (bins.size() != 4 || lo.size() != 4 || inv.size() != 4)
+    throw std::runtime_error("me_insert: the grid has 4 dimensions");
+  MeGrid grid;
+  long long C = 1;
+  for (int d = 0; d < 4; ++d) {
+    grid.bins[d] = bins[d].cast<int>();
+    grid.lo[d] = lo[d].cast<float>();
+    grid.inv[d] = inv[d].cast<float>();
+    if (grid.bins[d] < 1 || grid.bins[d] > ME_CELLS_MAX_HOST)
+      throw std::runtime_error("me_insert: bad bins");
+    C *= grid.bins[d];
+    if (C > ME_CELLS_MAX_HOST)
+      throw std::runtime_error("me_insert: too many cells");
+  }
+  if (pop < 1 || pop > GA_TRUNCATE_MAX_HOST)
+    throw std::runtime_error("me_insert: bad pop");
+  check(hipMemsetAsync((void*)best, 0, (size_t)C * 8, (hipStream_t)stream),
+        "me_insert memset");
+  hipLaunchKernelGGL(me_assign, dim3((unsigned)((pop + 255) / 256)),
+                     dim3(256), 0, (hipStream_t)stream,
+                     (const float*)fitness, (const float*)bc, pop, grid,
+                     (int*)cell, (unsigned long long*)best);
+  check(hipGetLastError(), "me_assign launch");
+  hipLaunchKernelGGL(me_commit, dim3((unsigned)((C + 1 + 255) / 256)),
+                     dim3(256), 0, (hipStream_t)stream,
+                     (const float*)fitness, (const float*)bc, pop, (int)C,
+                     (const unsigned long long*)best, (float*)arch_fitness,
+                     (float*)arch_bc, (int*)arch_filled, (int*)winner,
+                     (int*)order);
+  check(hipGetLastError(), "me_commit launch");
+}
+
+static void launch_me_compact(uintptr_t arch_filled, int C,
+                              uintptr_t filled_idx, uintptr_t n_filled,
+                              uintptr_t stream) {
+  if (C < 1 || C > ME_CELLS_MAX_HOST)
+    throw std::runtime_error("me_compact: bad C");
+  hipLaunchKernelGGL(me_compact, dim3(1), dim3(1024), 0, (hipStream_t)stream,
+                     (const int*)arch_filled, C, (int*)filled_idx,
+                     (int*)n_filled);
+  check(hipGetLastError(), "me_compact launch");
+}
+
 // ---- conv pipeline launchers ---------------------------------------------
 
 static void launch_perturb(uintptr_t theta, int nparams, int np_pad,
@@ -779,6 +890,26 @@ PYBIND11_MODULE(_ops, m) {
   m.def("ga_decode", &launch_ga_decode, py::arg("theta0"),
         py::arg("lineage"), py::arg("N"), py::arg("G"), py::arg("sigma"),
         py::arg("seed"), py::arg("thetas"), py::arg("stream"));
+  m.attr("ME_CELLS_MAX") = ME_CELLS_MAX_HOST;
+  m.def("me_parents", &launch_me_parents, py::arg("seed"), py::arg("gen"),
+        py::arg("pop"), py::arg("filled_idx"), py::arg("n_filled"),
+        py::arg("root_row"), py::arg("parent_idx"), py::arg("slot"),
+        py::arg("stream"));
+  m.def("ga_rollout_mlp_bc", &launch_ga_rollout_bc, py::arg("parents"),
+        py::arg("parent_idx"), py::arg("slot"), py::arg("sigma"),
+        py::arg("seed"), py::arg("gen"), py::arg("horizon"), py::arg("pop"),
+        py::arg("obs_mu"), py::arg("obs_nu"), py::arg("env_A"),
+        py::arg("env_B"), py::arg("fitness"), py::arg("obs_stat_part"),
+        py::arg("obs_stat"), py::arg("bc"), py::arg("final_states"),
+        py::arg("stream"));
+  m.def("me_insert", &launch_me_insert, py::arg("fitness"), py::arg("bc"),
+        py::arg("pop"), py::arg("bins"), py::arg("lo"), py::arg("inv"),
+        py::arg("arch_fitness"), py::arg("arch_bc"), py::arg("arch_filled"),
+        py::arg("best"), py::arg("cell"), py::arg("winner"),
+        py::arg("order"), py::arg("stream"));
+  m.def("me_compact", &launch_me_compact, py::arg("arch_filled"),
+        py::arg("C"), py::arg("filled_idx"), py::arg("n_filled"),
+        py::arg("stream"));
   m.def("pata_ec_codes", &launch_pata_ec_codes, py::arg("scores"),
         py::arg("K"), py::arg("M"), py::arg("Kpad"), py::arg("lo"),
         py::arg("hi"), py::arg("codes"), py::arg("stream"));

@@ -45,10 +45,8 @@
 // Philox tag of the parent draw; 0x45530001..3 are noise, env and conv obs.
 #define FAM_TAG_GA_PARENT 0x45530004u
 
-__device__ __forceinline__ float ga_mutate(float parent, float sigma,
-                                           float z) {
-  return fmaf(sigma, z, parent);
-}
+// ga_mutate and ga_rank_key, shared with me_kernels.hip
+#include "ga_shared.h"
 
 // Member m < n_elite is survivor m of the last generation, unmutated
 // (slot -1).  Every other member mutates a uniformly drawn survivor with the
@@ -165,13 +163,6 @@ ga_rollout_mlp(const float* __restrict__ parents,   // [T][NPARAMS]
 // milliseconds.
 // ---------------------------------------------------------------------------
 #define GA_TRUNC_TILE 2048
-
-__device__ __forceinline__ unsigned ga_rank_key(float f) {
-  if (f != f) return 0u;
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) == 0u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 extern "C" __global__ void __launch_bounds__(256)
 ga_truncate(const float* __restrict__ f, int n, int T,

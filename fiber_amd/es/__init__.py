@@ -6,6 +6,7 @@ from .engine import (  # noqa: F401
     make_env_params,
 )
 from .ga import GAConfig, GAEngine  # noqa: F401
+from .map_elites import MapElitesConfig, MapElitesEngine  # noqa: F401
 from .novelty import NoveltyConfig, NoveltyESEngine  # noqa: F401
 from .population import ESPopulation  # noqa: F401
 from .snes import SNESConfig, SNESEngine  # noqa: F401

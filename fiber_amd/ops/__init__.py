@@ -1088,5 +1088,300 @@ def ga_decode(theta0, lineage, sigma, seed, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------
+# MAP-Elites ops (me_kernels.hip): parents drawn from the filled cells of a
+# behaviour grid, the GA rollout with a behaviour characterisation, the
+# per-cell competition and the compact list of filled cells.  The archive's
+# weights are materialised by ga_survivors from the ``order`` that me_insert
+# writes.
+# ---------------------------------------------------------------------------
+
+# cells of the grid: the archive's rows and the root row ride grid.y
+ME_CELLS_MAX = _OPS.ME_CELLS_MAX if _OPS else GA_ROWS_MAX - 1
+
+
+def _check_me_bins(bins):
+    """The 4 bin counts as ints and their product C; ValueError unless every
+    count is >= 1 and ``C <= ME_CELLS_MAX``."""
+    try:
+        bins = tuple(int(b) for b in bins)
+    except TypeError:
+        raise ValueError("bins must be 4 ints, got %r" % (bins,))
+    if len(bins) != BC_DIM:
+        raise ValueError("bins must be %d ints, got %r" % (BC_DIM, bins))
+    C = 1
+    for b in bins:
+        if b < 1:
+            raise ValueError("every bins entry must be >= 1, got %r"
+                             % (bins,))
+        C *= b
+    if C + 1 > GA_ROWS_MAX:
+        raise ValueError("bins %r give %d cells, more than %d"
+                         % (bins, C, ME_CELLS_MAX))
+    return bins, C
+
+
+def me_grid(bins, lo, hi):
+    """The grid description me_insert passes to the device: ``(bins, lo32,
+    inv32, C)``, with ``lo32[d]`` the lower bound rounded to fp32 and
+    ``inv32[d] = bins[d] / (hi[d] - lo[d])`` computed in double precision
+    and then rounded to fp32, both returned as Python floats.
+
+    ValueError unless there are 4 dimensions, every ``bins[d] >= 1``, the
+    product ``C`` satisfies ``C + 1 <= GA_ROWS_MAX``, the bounds are finite
+    with ``hi[d] > lo[d]``, and ``inv32[d]`` is finite and positive."""
+    import numpy as np
+
+    bins, C = _check_me_bins(bins)
+    try:
+        lo = tuple(float(x) for x in lo)
+        hi = tuple(float(x) for x in hi)
+    except TypeError:
+        raise ValueError("lo and hi must be 4 floats each")
+    if len(lo) != BC_DIM or len(hi) != BC_DIM:
+        raise ValueError("lo and hi must be %d floats each, got %r and %r"
+                         % (BC_DIM, lo, hi))
+    lo32, inv32 = [], []
+    for d in range(BC_DIM):
+        if not (abs(lo[d]) < float("inf") and abs(hi[d]) < float("inf")):
+            raise ValueError("the bounds of dimension %d are not finite: "
+                             "[%r, %r]" % (d, lo[d], hi[d]))
+        if not hi[d] > lo[d]:
+            raise ValueError("need hi > lo in dimension %d, got [%r, %r]"
+                             % (d, lo[d], hi[d]))
+        with np.errstate(over="ignore"):
+            l32 = float(np.float32(lo[d]))
+            i32 = float(np.float32(np.float64(bins[d])
+                                   / (np.float64(hi[d]) - np.float64(lo[d]))))
+        if not (abs(l32) < float("inf") and 0.0 < i32 < float("inf")):
+            raise ValueError("the bounds of dimension %d, [%r, %r], leave "
+                             "the fp32 range" % (d, lo[d], hi[d]))
+        lo32.append(l32)
+        inv32.append(i32)
+    return bins, tuple(lo32), tuple(inv32), C
+
+
+def me_parents(seed, generation, pop, filled_idx, n_filled, root_row,
+               out_parent_idx=None, out_slot=None):
+    """Who mutates whom in one MAP-Elites generation: int32 ``(parent_idx[pop],
+    slot[pop])``.  Member ``m`` has ``slot = m`` and mutates the elite of cell
+    ``filled_idx[(u * n) >> 32]``, ``u`` the first word of one Philox draw
+    keyed by ``(seed, generation, m)`` and ``n`` the value of the one-element
+    int32 device tensor ``n_filled``, read on the device.  While ``n`` is 0
+    every parent is ``root_row``.  Integer arithmetic only:
+    ``map_elites_oracle.parents_exact`` reproduces it exactly.
+
+    The caller's contract: ``0 <= n <= filled_idx.numel()``, as ``me_compact``
+    writes it.  TypeError for dtype, device or contiguity; ValueError unless
+    ``1 <= pop <= GA_TRUNCATE_MAX``, ``filled_idx`` is 1-d and not empty,
+    ``n_filled`` has one element, ``0 <= root_row < 2**31`` and the outputs,
+    if given, are ``[pop]``."""
+    ops = _require_ops()
+    named = [("filled_idx", filled_idx, torch.int32),
+             ("n_filled", n_filled, torch.int32)]
+    if out_parent_idx is not None:
+        named.append(("out_parent_idx", out_parent_idx, torch.int32))
+    if out_slot is not None:
+        named.append(("out_slot", out_slot, torch.int32))
+    _check_ga_on(named, "filled_idx", filled_idx)
+    pop, root_row = int(pop), int(root_row)
+    if pop < 1 or pop > GA_TRUNCATE_MAX:
+        raise ValueError("pop must be in [1, %d], got %d"
+                         % (GA_TRUNCATE_MAX, pop))
+    if filled_idx.dim() != 1 or filled_idx.numel() < 1:
+        raise ValueError("filled_idx must be [C] with C >= 1, got %s"
+                         % (tuple(filled_idx.shape),))
+    if n_filled.numel() != 1:
+        raise ValueError("n_filled must hold one element, got %s"
+                         % (tuple(n_filled.shape),))
+    if root_row < 0 or root_row >= 2 ** 31:
+        raise ValueError("root_row must be in [0, 2**31), got %d" % root_row)
+    device = filled_idx.device
+    for name, t in (("out_parent_idx", out_parent_idx),
+                    ("out_slot", out_slot)):
+        if t is not None and tuple(t.shape) != (pop,):
+            raise ValueError("%s must be [%d], got %s"
+                             % (name, pop, tuple(t.shape)))
+    if out_parent_idx is None:
+        out_parent_idx = torch.empty(pop, dtype=torch.int32, device=device)
+    if out_slot is None:
+        out_slot = torch.empty(pop, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        ops.me_parents(int(seed) & 0xFFFFFFFF, int(generation) & 0xFFFFFFFF,
+                       pop, filled_idx.data_ptr(), n_filled.data_ptr(),
+                       root_row, out_parent_idx.data_ptr(),
+                       out_slot.data_ptr(), _stream())
+    return out_parent_idx, out_slot
+
+
+def ga_rollout_mlp_bc(parents, parent_idx, slot, sigma, seed, generation,
+                      horizon, obs_mu, obs_nu, env_A, env_B,
+                      return_final_states=False):
+    """``ga_rollout_mlp`` that also reports each member's behaviour
+    characterisation ``bc[pop][4]``, the mean over the member's 64 episodes
+    of the final state, summed in a fixed order.
+
+    Returns ``(fitness, obs_stat, bc)``, or ``(fitness, obs_stat, bc,
+    final_states[pop][64][4])``.  ``fitness`` and ``obs_stat`` are
+    bit-identical to ``ga_rollout_mlp`` for the same arguments; the BC of a
+    mutated member is that of ``es_rollout_mlp_bc``'s member ``2 * slot`` for
+    the same parent, the BC of an unmutated one that of ``es_eval_bc`` for
+    its row.
+
+    Contract and validation as ``ga_rollout_mlp``."""
+    ops = _require_ops()
+    _check_ga_on(
+        (("parents", parents, torch.float32),
+         ("parent_idx", parent_idx, torch.int32),
+         ("slot", slot, torch.int32), ("obs_mu", obs_mu, torch.float32),
+         ("obs_nu", obs_nu, torch.float32), ("env_A", env_A, torch.float32),
+         ("env_B", env_B, torch.float32)), "parents", parents)
+    if parents.dim() != 2 or parents.shape[1] != NPARAMS \
+            or parents.shape[0] < 1:
+        raise ValueError("parents must be [T, %d] with T >= 1, got %s"
+                         % (NPARAMS, tuple(parents.shape)))
+    if parent_idx.dim() != 1 or parent_idx.numel() < 1:
+        raise ValueError("parent_idx must be [pop] with pop >= 1, got %s"
+                         % (tuple(parent_idx.shape),))
+    pop = parent_idx.numel()
+    for name, t, want in (("slot", slot, (pop,)),
+                          ("obs_mu", obs_mu, (OBS_DIM,)),
+                          ("obs_nu", obs_nu, (OBS_DIM,)),
+                          ("env_A", env_A, (OBS_DIM, OBS_DIM)),
+                          ("env_B", env_B, (OBS_DIM,))):
+        if tuple(t.shape) != want:
+            raise ValueError("%s must be %s, got %s"
+                             % (name, list(want), tuple(t.shape)))
+    horizon = int(horizon)
+    if horizon < 1:
+        raise ValueError("horizon must be >= 1, got %d" % horizon)
+    if pop >= 2 ** 31:
+        raise ValueError("pop = %d exceeds the launch grid" % pop)
+    sigma = _check_ga_sigma(sigma)
+    device = parents.device
+    fitness = torch.empty(pop, dtype=torch.float32, device=device)
+    obs_stat = torch.zeros(2 * OBS_DIM + 1, dtype=torch.float32,
+                           device=device)
+    bc = torch.empty(pop, BC_DIM, dtype=torch.float32, device=device)
+    final = None
+    if return_final_states:
+        final = torch.empty(pop, ENVS_PER_MEMBER, OBS_DIM,
+                            dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        part = _partial_buffer(device, pop * 2 * OBS_DIM)
+        ops.ga_rollout_mlp_bc(
+            parents.data_ptr(), parent_idx.data_ptr(), slot.data_ptr(),
+            sigma, int(seed) & 0xFFFFFFFF, int(generation) & 0xFFFFFFFF,
+            horizon, pop, obs_mu.data_ptr(), obs_nu.data_ptr(),
+            env_A.data_ptr(), env_B.data_ptr(), fitness.data_ptr(),
+            part.data_ptr(), obs_stat.data_ptr(), bc.data_ptr(),
+            final.data_ptr() if return_final_states else 0, _stream())
+    if return_final_states:
+        return fitness, obs_stat, bc, final
+    return fitness, obs_stat, bc
+
+
+def me_insert(fitness, bc, bins, lo, hi, arch_fitness, arch_bc, arch_filled):
+    """One generation's competition for the cells of the archive, in place.
+
+    The cell of member ``m``: per dimension ``t = (bc[m][d] - lo32[d]) *
+    inv32[d]`` in fp32, each operation rounded once (``me_grid`` gives
+    ``lo32`` and ``inv32``), ``b_d = clamp(floor(t), 0, bins[d] - 1)``, and
+    ``cell = ((b_0 * bins[1] + b_1) * bins[2] + b_2) * bins[3] + b_3``.  A
+    member with a NaN in its BC or a NaN fitness has cell -1 and is never
+    inserted.  The winner of a cell is the fittest child that lands in it,
+    in ``ga_truncate``'s order (-0 equals +0), the lower member index among
+    equals; it displaces the occupant only if it is strictly fitter.
+
+    Updates ``arch_fitness[C]``, ``arch_bc[C][4]`` (the winner's bits) and
+    int32 ``arch_filled[C]``, and returns int32 ``(cell[pop], winner[C],
+    order[C + 1])``: ``winner[c]`` is the member index or -1 where the cell
+    is unchanged, and ``order[c] = winner[c] if winner[c] >= 0 else pop + c``
+    with ``order[C] = pop + C``, which ``ga_survivors`` turns into the
+    archive's weights when ``parent_idx`` and ``slot`` are extended by ``C +
+    1`` pseudo-members (parent ``c``, slot -1).  The result does not depend
+    on scheduling.
+
+    TypeError for dtype, device or contiguity; ValueError for shapes, a
+    ``bins`` entry below 1, ``C + 1 > GA_ROWS_MAX``, bounds that are not
+    finite or not ``hi > lo``, or ``pop`` outside ``[1, GA_TRUNCATE_MAX]``."""
+    ops = _require_ops()
+    _check_ga_on((("fitness", fitness, torch.float32),
+                  ("bc", bc, torch.float32),
+                  ("arch_fitness", arch_fitness, torch.float32),
+                  ("arch_bc", arch_bc, torch.float32),
+                  ("arch_filled", arch_filled, torch.int32)),
+                 "fitness", fitness)
+    bins, lo32, inv32, C = me_grid(bins, lo, hi)
+    if fitness.dim() != 1:
+        raise ValueError("fitness must be 1-d, got %s"
+                         % (tuple(fitness.shape),))
+    pop = fitness.numel()
+    if pop < 1 or pop > GA_TRUNCATE_MAX:
+        raise ValueError("pop must be in [1, %d], got %d"
+                         % (GA_TRUNCATE_MAX, pop))
+    for name, t, want in (("bc", bc, (pop, BC_DIM)),
+                          ("arch_fitness", arch_fitness, (C,)),
+                          ("arch_bc", arch_bc, (C, BC_DIM)),
+                          ("arch_filled", arch_filled, (C,))):
+        if tuple(t.shape) != want:
+            raise ValueError("%s must be %s, got %s"
+                             % (name, list(want), tuple(t.shape)))
+    for name, t in (("bc", bc), ("arch_bc", arch_bc)):
+        if t.data_ptr() % 16:
+            raise ValueError("%s must be 16-byte aligned" % name)
+    device = fitness.device
+    cell = torch.empty(pop, dtype=torch.int32, device=device)
+    winner = torch.empty(C, dtype=torch.int32, device=device)
+    order = torch.empty(C + 1, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        best = torch.empty(C, dtype=torch.int64, device=device)
+        ops.me_insert(fitness.data_ptr(), bc.data_ptr(), pop, bins, lo32,
+                      inv32, arch_fitness.data_ptr(), arch_bc.data_ptr(),
+                      arch_filled.data_ptr(), best.data_ptr(),
+                      cell.data_ptr(), winner.data_ptr(), order.data_ptr(),
+                      _stream())
+    return cell, winner, order
+
+
+def me_compact(arch_filled, out_filled_idx=None, out_n_filled=None):
+    """The compact list of filled cells, in one launch and without a host
+    sync: int32 ``(filled_idx[C], n_filled[1])`` with ``filled_idx[0 ..
+    n_filled)`` the indices ``c`` with ``arch_filled[c] != 0`` in ascending
+    order and -1 behind them.
+
+    TypeError for dtype, device or contiguity; ValueError unless
+    ``arch_filled`` is 1-d with ``1 <= C <= ME_CELLS_MAX`` and the outputs,
+    if given, are ``[C]`` and one element."""
+    ops = _require_ops()
+    named = [("arch_filled", arch_filled, torch.int32)]
+    if out_filled_idx is not None:
+        named.append(("out_filled_idx", out_filled_idx, torch.int32))
+    if out_n_filled is not None:
+        named.append(("out_n_filled", out_n_filled, torch.int32))
+    _check_ga_on(named, "arch_filled", arch_filled)
+    if arch_filled.dim() != 1:
+        raise ValueError("arch_filled must be 1-d, got %s"
+                         % (tuple(arch_filled.shape),))
+    C = arch_filled.numel()
+    if C < 1 or C > ME_CELLS_MAX:
+        raise ValueError("C must be in [1, %d], got %d" % (ME_CELLS_MAX, C))
+    device = arch_filled.device
+    if out_filled_idx is None:
+        out_filled_idx = torch.empty(C, dtype=torch.int32, device=device)
+    elif tuple(out_filled_idx.shape) != (C,):
+        raise ValueError("out_filled_idx must be [%d], got %s"
+                         % (C, tuple(out_filled_idx.shape)))
+    if out_n_filled is None:
+        out_n_filled = torch.empty(1, dtype=torch.int32, device=device)
+    elif out_n_filled.numel() != 1:
+        raise ValueError("out_n_filled must hold one element, got %s"
+                         % (tuple(out_n_filled.shape),))
+    with torch.cuda.device(device):
+        ops.me_compact(arch_filled.data_ptr(), C, out_filled_idx.data_ptr(),
+                       out_n_filled.data_ptr(), _stream())
+    return out_filled_idx, out_n_filled
+
+
 def ops_available():
     return _OPS is not None

@@ -53,6 +53,10 @@ class build_ext(_build_ext):
             # arrangement
             os.path.join(ROOT, "fiber_amd", "csrc", "ops",
                          "ga_kernels.hip"),
+            # MAP-Elites rollout with a BC, archive insert and compaction:
+            # the same arrangement
+            os.path.join(ROOT, "fiber_amd", "csrc", "ops",
+                         "me_kernels.hip"),
             # PATA-EC novelty kernels: shares nothing with the rollout
             # kernels and stays out of their register allocation
             os.path.join(ROOT, "fiber_amd", "csrc", "ops",
@@ -63,6 +67,9 @@ class build_ext(_build_ext):
         ]
         hdrs = [
             os.path.join(ROOT, "fiber_amd", "csrc", "ops", "philox.h"),
+            os.path.join(ROOT, "fiber_amd", "csrc", "ops", "ga_shared.h"),
+            os.path.join(ROOT, "fiber_amd", "csrc", "ops", "bc_epilogue.h"),
+            os.path.join(ROOT, "fiber_amd", "csrc", "ops", "me_grid.h"),
         ]
         if os.path.exists(out):
             newest_src = max(os.path.getmtime(s) for s in srcs + hdrs)
