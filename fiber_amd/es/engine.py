@@ -201,6 +201,40 @@ class ESEngine:
             return scores.reshape(()), episodes.reshape(-1)
         return out.reshape(())
 
+    # -- act with the current policy --------------------------------------
+    def act(self, obs, return_logits=False):
+        """Actions of the current, unperturbed theta for raw observations
+        ``obs[n][4]`` (fp32, on this engine's device), as the rollout
+        kernels would choose them: the observation is normalised with the
+        engine's ``obs_mu`` / ``obs_nu`` by the kernel's formula,
+        ``(obs - mu) * rsqrt(nu + 1e-4)`` clamped to +-5 in fp32, and goes
+        through ``ops.mlp_policy_forward``.  Returns int64 ``actions[n]``,
+        1 where ``logits[:, 1] > logits[:, 0]`` and 0 otherwise (a tie is
+        0, as in the step loop), or ``(actions, logits)``.
+
+        The serving kernel rounds ``h2`` to bf16, the step loop does not:
+        where ``|l1 - l0|`` is under ``sum_i |w3[1][i] - w3[0][i]| *
+        spacing(h2_i) / 2`` the two may choose differently
+        (profiles/forward_oracle.md)."""
+        if not torch.is_tensor(obs):
+            raise TypeError("obs must be a tensor, got %s"
+                            % type(obs).__name__)
+        if obs.dim() != 2 or obs.shape[1] != self.cfg.obs_dim:
+            raise ValueError("obs must be [n, %d], got %s"
+                             % (self.cfg.obs_dim, tuple(obs.shape)))
+        if obs.dtype != torch.float32:
+            raise TypeError("obs must be torch.float32, got %s" % obs.dtype)
+        if obs.device != self.theta.device:
+            raise TypeError("obs is on %s, the engine on %s"
+                            % (obs.device, self.theta.device))
+        rstd = torch.rsqrt(self.obs_nu + 1e-4)
+        x = ((obs - self.obs_mu) * rstd).clamp_(-5.0, 5.0).contiguous()
+        logits = ops.mlp_policy_forward(self.theta, x)
+        actions = (logits[:, 1] > logits[:, 0]).to(torch.int64)
+        if return_logits:
+            return actions, logits
+        return actions
+
     # -- checkpoint / resume ----------------------------------------------
     # (the reference has no checkpointing — SURVEY §5; this is additive.)
     def state_dict(self):

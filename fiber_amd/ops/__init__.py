@@ -196,16 +196,59 @@ def centered_rank_ref(fitness):
     return order.float() / (n - 1) - 0.5
 
 
-def mlp_policy_forward(theta, x):
-    """Batched policy forward logits via the MFMA path."""
+def _check_forward_batch(batch):
+    """The kernel indexes ``x`` with a 32-bit ``row * OBS_DIM + d``."""
+    if batch < 0 or batch * OBS_DIM >= 2 ** 31:
+        raise ValueError("batch = %d: row * %d leaves the int32 index range"
+                         % (batch, OBS_DIM))
+    return batch
+
+
+def mlp_policy_forward(theta, x, out=None):
+    """Batched policy forward via the MFMA path: ``logits[batch][2]`` for
+    ``x[batch][4]`` and the flat ``theta[NPARAMS]``, all fp32 on one device.
+
+    ``x`` is used as it is: the rollout kernels feed the policy the
+    normalised, clamped observation, and so must the caller
+    (``ESEngine.act`` does).  ``x``, ``h1`` and ``h2`` are rounded to bf16;
+    the rollout step loop keeps ``h2`` in fp32, so its logits differ from
+    these by up to ``sum_i |w3[a][i]| * spacing(h2_i) / 2``
+    (profiles/forward_oracle.md).
+
+    ``out``, if given, is contiguous fp32 ``[batch][2]`` storage on the
+    device of ``x``; it is written and returned.  Rows are independent: a
+    non-finite row of ``x`` gives non-finite logits in that row only.
+    ``batch == 0`` returns an empty ``[0][2]`` tensor without a launch.
+
+    Everything is validated before the launch: TypeError for dtype, device
+    or contiguity, ValueError for a shape or a batch past the kernel's
+    32-bit index."""
     ops = _require_ops()
-    _check(theta, "theta")
-    _check(x, "x")
-    batch = x.shape[0]
-    logits = torch.empty(batch, ACT_DIM, dtype=torch.float32,
-                         device=x.device)
-    ops.mlp_policy_forward(theta.data_ptr(), x.data_ptr(), batch,
-                           logits.data_ptr(), _stream())
+    named = [("theta", theta), ("x", x)]
+    if out is not None:
+        named.append(("out", out))
+    for name, t in named:
+        _check(t, name)
+        if t.device != x.device:
+            raise TypeError("%s is on %s, x on %s"
+                            % (name, t.device, x.device))
+    if tuple(theta.shape) != (NPARAMS,):
+        raise ValueError("theta must be [%d], got %s"
+                         % (NPARAMS, tuple(theta.shape)))
+    if x.dim() != 2 or x.shape[1] != OBS_DIM:
+        raise ValueError("x must be [batch, %d], got %s"
+                         % (OBS_DIM, tuple(x.shape)))
+    batch = _check_forward_batch(x.shape[0])
+    if out is not None and tuple(out.shape) != (batch, ACT_DIM):
+        raise ValueError("out must be [%d, %d], got %s"
+                         % (batch, ACT_DIM, tuple(out.shape)))
+    logits = out if out is not None else torch.empty(
+        batch, ACT_DIM, dtype=torch.float32, device=x.device)
+    if batch == 0:
+        return logits
+    with torch.cuda.device(x.device):
+        ops.mlp_policy_forward(theta.data_ptr(), x.data_ptr(), batch,
+                               logits.data_ptr(), _stream())
     return logits
 
 
