@@ -84,6 +84,16 @@ extern "C" __global__ void ga_survivors(const float*, const int*, const int*,
                                         float*);
 extern "C" __global__ void ga_decode(const float*, const int*, int, float,
                                      uint32_t, float*);
+// safe-mutation kernels (sm_kernels.hip)
+extern "C" __global__ void sm_steps(const float*, const float*, float, float,
+                                    int, float*, float*);
+extern "C" __global__ void ga_rollout_mlp_sm(
+    const float*, const float*, const int*, const int*, uint32_t, uint32_t,
+    int, const float*, const float*, const float*, const float*, float*,
+    float*, float*);
+extern "C" __global__ void ga_survivors_sm(const float*, const float*,
+                                           const int*, const int*, const int*,
+                                           uint32_t, uint32_t, float*);
 // MAP-Elites kernels (me_kernels.hip)
 extern "C" __global__ void me_parents(uint32_t, uint32_t, int, const int*,
                                       const int*, int, int*, int*);
@@ -582,6 +592,68 @@ static void launch_ga_decode(uintptr_t theta0, uintptr_t lineage, int N,
   check(hipGetLastError(), "ga_decode launch");
 }
 
+// ---- safe-mutation launchers -------------------------------------------------
+static void launch_sm_steps(uintptr_t thetas, uintptr_t probe, int T,
+                            double sigma, double s_min, int mode,
+                            uintptr_t steps, uintptr_t sens,
+                            uintptr_t stream) {
+  if (T < 1 || T > GA_ROWS_MAX_HOST)
+    throw std::runtime_error("sm_steps: bad T");
+  if (mode != 0 && mode != 1) throw std::runtime_error("sm_steps: bad mode");
+  if (!(sigma >= 0.0) || !(s_min > 0.0))
+    throw std::runtime_error("sm_steps: bad sigma or s_min");
+  hipLaunchKernelGGL(sm_steps, dim3(T), dim3(256), 0, (hipStream_t)stream,
+                     (const float*)thetas, (const float*)probe, (float)sigma,
+                     (float)s_min, mode, (float*)steps, (float*)sens);
+  check(hipGetLastError(), "sm_steps launch");
+}
+
+// launch_ga_rollout with a step row per parent.
+static void launch_ga_rollout_sm(uintptr_t parents, uintptr_t steps,
+                                 uintptr_t parent_idx, uintptr_t slot,
+                                 uint32_t seed, uint32_t gen, int horizon,
+                                 int pop, uintptr_t obs_mu, uintptr_t obs_nu,
+                                 uintptr_t env_A, uintptr_t env_B,
+                                 uintptr_t fitness, uintptr_t obs_stat_part,
+                                 uintptr_t obs_stat, uintptr_t stream) {
+  if (pop < 1)
+    throw std::runtime_error("ga_rollout_mlp_sm: pop must be >= 1");
+  if (horizon < 1)
+    throw std::runtime_error("ga_rollout_mlp_sm: horizon must be >= 1");
+  hipLaunchKernelGGL(ga_rollout_mlp_sm, dim3(pop), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)parents,
+                     (const float*)steps, (const int*)parent_idx,
+                     (const int*)slot, seed, gen, horizon,
+                     (const float*)obs_mu, (const float*)obs_nu,
+                     (const float*)env_A, (const float*)env_B,
+                     (float*)fitness, (float*)obs_stat_part,
+                     (float*)obs_stat);
+  check(hipGetLastError(), "ga_rollout_mlp_sm launch");
+  hipLaunchKernelGGL(obs_stat_reduce, dim3(2 * OBS_HOST), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)obs_stat_part, pop,
+                     (float*)obs_stat);
+  check(hipGetLastError(), "obs_stat_reduce launch");
+}
+
+static void launch_ga_survivors_sm(uintptr_t parents, uintptr_t steps,
+                                   uintptr_t parent_idx, uintptr_t slot,
+                                   uintptr_t order, int T, uint32_t seed,
+                                   uint32_t gen, uintptr_t new_parents,
+                                   uintptr_t stream) {
+  if (T < 1 || T > GA_ROWS_MAX_HOST)
+    throw std::runtime_error("ga_survivors_sm: bad T");
+  if (parents == new_parents || steps == new_parents)
+    throw std::runtime_error(
+        "ga_survivors_sm: new_parents aliases parents or steps");
+  const int bx = ((NPARAMS_HOST + 3) / 4 + 255) / 256;
+  hipLaunchKernelGGL(ga_survivors_sm, dim3(bx, T), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)parents,
+                     (const float*)steps, (const int*)parent_idx,
+                     (const int*)slot, (const int*)order, seed, gen,
+                     (float*)new_parents);
+  check(hipGetLastError(), "ga_survivors_sm launch");
+}
+
 // ---- MAP-Elites launchers ---------------------------------------------------
 // The archive's rows ride grid.y of ga_survivors and ga_decode with the root
 // row behind them, so C + 1 <= GA_ROWS_MAX.
@@ -890,6 +962,19 @@ PYBIND11_MODULE(_ops, m) {
   m.def("ga_decode", &launch_ga_decode, py::arg("theta0"),
         py::arg("lineage"), py::arg("N"), py::arg("G"), py::arg("sigma"),
         py::arg("seed"), py::arg("thetas"), py::arg("stream"));
+  m.def("sm_steps", &launch_sm_steps, py::arg("thetas"), py::arg("probe"),
+        py::arg("T"), py::arg("sigma"), py::arg("s_min"), py::arg("mode"),
+        py::arg("steps"), py::arg("sens"), py::arg("stream"));
+  m.def("ga_rollout_mlp_sm", &launch_ga_rollout_sm, py::arg("parents"),
+        py::arg("steps"), py::arg("parent_idx"), py::arg("slot"),
+        py::arg("seed"), py::arg("gen"), py::arg("horizon"), py::arg("pop"),
+        py::arg("obs_mu"), py::arg("obs_nu"), py::arg("env_A"),
+        py::arg("env_B"), py::arg("fitness"), py::arg("obs_stat_part"),
+        py::arg("obs_stat"), py::arg("stream"));
+  m.def("ga_survivors_sm", &launch_ga_survivors_sm, py::arg("parents"),
+        py::arg("steps"), py::arg("parent_idx"), py::arg("slot"),
+        py::arg("order"), py::arg("T"), py::arg("seed"), py::arg("gen"),
+        py::arg("new_parents"), py::arg("stream"));
   m.attr("ME_CELLS_MAX") = ME_CELLS_MAX_HOST;
   m.def("me_parents", &launch_me_parents, py::arg("seed"), py::arg("gen"),
         py::arg("pop"), py::arg("filled_idx"), py::arg("n_filled"),

@@ -36,7 +36,8 @@ Out of scope: the paper's separate 30-episode re-evaluation of the elite
 candidates (every member here already averages 64 episodes; the elites are
 re-scored with everyone else on each generation's start states), crossover,
 an adaptive or per-parameter sigma, the conv engine, ``ESPopulation`` and
-multi-process runs.
+multi-process runs.  A per-parent, per-parameter step from output gradients
+(safe mutations) is ``SafeGAEngine`` in fiber_amd/es/safe_ga.py.
 """
 
 import dataclasses

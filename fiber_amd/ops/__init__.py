@@ -1132,6 +1132,212 @@ def ga_decode(theta0, lineage, sigma, seed, out=None):
 
 
 # ---------------------------------------------------------------------------
+# Safe mutations (sm_kernels.hip): per-parent, per-parameter mutation steps
+# from the sensitivity of the logits on a probe batch, and the GA rollout /
+# survivors kernels that take such a step row per parent instead of one
+# scalar sigma.
+# ---------------------------------------------------------------------------
+
+SM_MODES = ("abs", "sum")
+SM_PROBE_ROWS = ENVS_PER_MEMBER
+
+
+def _check_sm_mode(mode):
+    if mode not in SM_MODES:
+        raise ValueError("mode must be one of %r, got %r" % (SM_MODES, mode))
+    return SM_MODES.index(mode)
+
+
+def _check_sm_floor(s_min):
+    s_min = float(s_min)
+    if not 0.0 < s_min < float("inf"):  # also refuses a NaN
+        raise ValueError("s_min must be finite and > 0, got %r" % s_min)
+    return s_min
+
+
+def _check_overlap(out, other, other_name, op):
+    lo, hi = out.data_ptr(), out.data_ptr() + out.numel() * 4
+    plo = other.data_ptr()
+    phi = plo + other.numel() * 4
+    if lo < phi and plo < hi:
+        raise ValueError("out overlaps %s: %s is out of place"
+                         % (other_name, op))
+
+
+def sm_steps(thetas, probe, sigma, s_min=0.01, mode="abs", out=None,
+             return_sens=False):
+    """Safe-mutation steps of ``thetas[T][NPARAMS]`` on ``probe[64][4]``
+    (normalised observations): ``steps[t][j] = sigma / max(sens[t][j],
+    s_min)`` with ``sens = sqrt(m_0^2 + m_1^2)`` and ``m_k[j]`` the mean
+    over the probe rows of ``|d logit_k / d theta_j|`` (``mode="abs"``) or
+    of the signed derivative (``mode="sum"``).  One workgroup per row; row
+    ``t`` of the result depends on row ``t`` of ``thetas`` only.  Returns
+    ``steps``, or ``(steps, sens)`` with ``return_sens``.  ``out``, if
+    given, is fp32 ``[T][NPARAMS]`` storage for ``steps``.  ``T = 0`` gives
+    empty results.
+
+    TypeError for dtype, device or contiguity, ValueError for shapes, ``T >
+    65535``, a sigma that is negative or not finite, an ``s_min`` that is
+    not finite and positive, or an unknown mode."""
+    ops = _require_ops()
+    # the scalars first: they need no tensor to be judged
+    sigma = _check_ga_sigma(sigma)
+    s_min = _check_sm_floor(s_min)
+    mode_id = _check_sm_mode(mode)
+    named = [("thetas", thetas, torch.float32),
+             ("probe", probe, torch.float32)]
+    if out is not None:
+        named.append(("out", out, torch.float32))
+    _check_ga_on(named, "thetas", thetas)
+    if thetas.dim() != 2 or thetas.shape[1] != NPARAMS:
+        raise ValueError("thetas must be [T, %d], got %s"
+                         % (NPARAMS, tuple(thetas.shape)))
+    if tuple(probe.shape) != (SM_PROBE_ROWS, OBS_DIM):
+        raise ValueError("probe must be [%d, %d], got %s"
+                         % (SM_PROBE_ROWS, OBS_DIM, tuple(probe.shape)))
+    T = thetas.shape[0]
+    if T > GA_ROWS_MAX:
+        raise ValueError("T must be <= %d, got %d" % (GA_ROWS_MAX, T))
+    device = thetas.device
+    if out is None:
+        out = torch.empty(T, NPARAMS, dtype=torch.float32, device=device)
+    else:
+        if tuple(out.shape) != (T, NPARAMS):
+            raise ValueError("out must be [%d, %d], got %s"
+                             % (T, NPARAMS, tuple(out.shape)))
+        _check_overlap(out, thetas, "thetas", "sm_steps")
+    sens = (torch.empty(T, NPARAMS, dtype=torch.float32, device=device)
+            if return_sens else None)
+    if T > 0:
+        with torch.cuda.device(device):
+            ops.sm_steps(thetas.data_ptr(), probe.data_ptr(), T, sigma,
+                         s_min, mode_id, out.data_ptr(),
+                         sens.data_ptr() if return_sens else 0, _stream())
+    return (out, sens) if return_sens else out
+
+
+def _check_sm_steps_rows(steps, parents):
+    if tuple(steps.shape) != tuple(parents.shape):
+        raise ValueError("steps must have the shape of parents %s, got %s"
+                         % (tuple(parents.shape), tuple(steps.shape)))
+
+
+def ga_rollout_mlp_sm(parents, steps, parent_idx, slot, seed, generation,
+                      horizon, obs_mu, obs_nu, env_A, env_B):
+    """``ga_rollout_mlp`` with a step row per parent: a mutated member is
+    ``parent[j] + steps[parent_idx[m]][j] * z[j]`` in one fma, ``z`` the
+    draw of child slot ``slot[m]``; ``slot[m] < 0`` takes the row as it is.
+    With every step equal to ``sigma`` the result carries the bits of
+    ``ga_rollout_mlp``.  Returns ``(fitness[pop], obs_stat[9])``.
+
+    The caller's contract and the validation are ``ga_rollout_mlp``'s;
+    ``steps`` is fp32 with the shape of ``parents`` (``sm_steps`` writes
+    it), finite where a member is mutated."""
+    ops = _require_ops()
+    _check_ga_on(
+        (("parents", parents, torch.float32),
+         ("steps", steps, torch.float32),
+         ("parent_idx", parent_idx, torch.int32),
+         ("slot", slot, torch.int32), ("obs_mu", obs_mu, torch.float32),
+         ("obs_nu", obs_nu, torch.float32), ("env_A", env_A, torch.float32),
+         ("env_B", env_B, torch.float32)), "parents", parents)
+    if parents.dim() != 2 or parents.shape[1] != NPARAMS \
+            or parents.shape[0] < 1:
+        raise ValueError("parents must be [T, %d] with T >= 1, got %s"
+                         % (NPARAMS, tuple(parents.shape)))
+    _check_sm_steps_rows(steps, parents)
+    if parent_idx.dim() != 1 or parent_idx.numel() < 1:
+        raise ValueError("parent_idx must be [pop] with pop >= 1, got %s"
+                         % (tuple(parent_idx.shape),))
+    pop = parent_idx.numel()
+    for name, t, want in (("slot", slot, (pop,)),
+                          ("obs_mu", obs_mu, (OBS_DIM,)),
+                          ("obs_nu", obs_nu, (OBS_DIM,)),
+                          ("env_A", env_A, (OBS_DIM, OBS_DIM)),
+                          ("env_B", env_B, (OBS_DIM,))):
+        if tuple(t.shape) != want:
+            raise ValueError("%s must be %s, got %s"
+                             % (name, list(want), tuple(t.shape)))
+    horizon = int(horizon)
+    if horizon < 1:
+        raise ValueError("horizon must be >= 1, got %d" % horizon)
+    if pop >= 2 ** 31:
+        raise ValueError("pop = %d exceeds the launch grid" % pop)
+    device = parents.device
+    fitness = torch.empty(pop, dtype=torch.float32, device=device)
+    obs_stat = torch.zeros(2 * OBS_DIM + 1, dtype=torch.float32,
+                           device=device)
+    with torch.cuda.device(device):
+        part = _partial_buffer(device, pop * 2 * OBS_DIM)
+        ops.ga_rollout_mlp_sm(
+            parents.data_ptr(), steps.data_ptr(), parent_idx.data_ptr(),
+            slot.data_ptr(), int(seed) & 0xFFFFFFFF,
+            int(generation) & 0xFFFFFFFF, horizon, pop, obs_mu.data_ptr(),
+            obs_nu.data_ptr(), env_A.data_ptr(), env_B.data_ptr(),
+            fitness.data_ptr(), part.data_ptr(), obs_stat.data_ptr(),
+            _stream())
+    return fitness, obs_stat
+
+
+def ga_survivors_sm(parents, steps, parent_idx, slot, order, seed,
+                    generation, out=None):
+    """``ga_survivors`` with a step row per parent: row ``t`` of the result
+    is the weights member ``order[t]`` of ``ga_rollout_mlp_sm``'s launch
+    from the same arguments was evaluated with.  Out of place: ``out``, if
+    given, is fp32 ``[T][NPARAMS]`` storage that shares no memory with
+    ``parents`` or ``steps``.
+
+    One generation ``c`` of a seed-chain decode over ``N`` rows is
+    ``ga_survivors_sm(rows, sm_steps(rows), arange(N), lineage[:, c],
+    arange(N), seed, c)``.
+
+    Contract and validation are ``ga_survivors``'s; ``steps`` is fp32 with
+    the shape of ``parents``."""
+    ops = _require_ops()
+    named = [("parents", parents, torch.float32),
+             ("steps", steps, torch.float32),
+             ("parent_idx", parent_idx, torch.int32),
+             ("slot", slot, torch.int32), ("order", order, torch.int32)]
+    if out is not None:
+        named.append(("out", out, torch.float32))
+    _check_ga_on(named, "parents", parents)
+    if parents.dim() != 2 or parents.shape[1] != NPARAMS \
+            or parents.shape[0] < 1:
+        raise ValueError("parents must be [T_cur, %d] with T_cur >= 1, got %s"
+                         % (NPARAMS, tuple(parents.shape)))
+    _check_sm_steps_rows(steps, parents)
+    if parent_idx.dim() != 1 or parent_idx.numel() < 1:
+        raise ValueError("parent_idx must be [pop] with pop >= 1, got %s"
+                         % (tuple(parent_idx.shape),))
+    pop = parent_idx.numel()
+    if tuple(slot.shape) != (pop,):
+        raise ValueError("slot must be [%d], got %s"
+                         % (pop, tuple(slot.shape)))
+    if order.dim() != 1:
+        raise ValueError("order must be 1-d, got %s" % (tuple(order.shape),))
+    T = order.numel()
+    if T < 1 or T > GA_ROWS_MAX or T > pop:
+        raise ValueError("T must be in [1, min(pop, %d)], got %d"
+                         % (GA_ROWS_MAX, T))
+    device = parents.device
+    if out is None:
+        out = torch.empty(T, NPARAMS, dtype=torch.float32, device=device)
+    else:
+        if tuple(out.shape) != (T, NPARAMS):
+            raise ValueError("out must be [%d, %d], got %s"
+                             % (T, NPARAMS, tuple(out.shape)))
+        _check_overlap(out, parents, "parents", "ga_survivors_sm")
+        _check_overlap(out, steps, "steps", "ga_survivors_sm")
+    with torch.cuda.device(device):
+        ops.ga_survivors_sm(parents.data_ptr(), steps.data_ptr(),
+                            parent_idx.data_ptr(), slot.data_ptr(),
+                            order.data_ptr(), T, int(seed) & 0xFFFFFFFF,
+                            int(generation) & 0xFFFFFFFF, out.data_ptr(),
+                            _stream())
+    return out
+
+
+# ---------------------------------------------------------------------------
 # MAP-Elites ops (me_kernels.hip): parents drawn from the filled cells of a
 # behaviour grid, the GA rollout with a behaviour characterisation, the
 # per-cell competition and the compact list of filled cells.  The archive's

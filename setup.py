@@ -53,6 +53,11 @@ class build_ext(_build_ext):
             # arrangement
             os.path.join(ROOT, "fiber_amd", "csrc", "ops",
                          "ga_kernels.hip"),
+            # safe-mutation steps (forward + backward of the policy) and
+            # the GA rollout / survivors with a step row per parent: the
+            # same arrangement
+            os.path.join(ROOT, "fiber_amd", "csrc", "ops",
+                         "sm_kernels.hip"),
             # MAP-Elites rollout with a BC, archive insert and compaction:
             # the same arrangement
             os.path.join(ROOT, "fiber_amd", "csrc", "ops",
