@@ -359,3 +359,79 @@ def test_es_population_step_against_step_fp64():
                           _snapshot(pop, MLP_FIELDS, p), MLP_FIELDS, worst)
     print("ESPopulation P = %d: max err/tol per field %s"
           % (len(seeds), {k: round(v, 4) for k, v in worst.items()}))
+
+
+@requires_gpu
+def test_es_engine_step_takes_the_variance_floor():
+    """One real step() on which the 1e-2 variance floor is the value taken
+    (dims 0 and 1; the state is update_oracle_cases.floor_obs_state, chosen
+    on the CPU), every field as above and obs_nu on the floor bit for bit.
+    Then the +-5 clamp of the normalised obs under that engine's own
+    normaliser: one more rollout pair of its theta, held one step at a
+    time as in test_rollout_step_gpu.py."""
+    import rollout_step_cases as S
+    from fiber_amd import ops
+    from fiber_amd.es import rollout_oracle
+    from fiber_amd.es.engine import ESConfig, ESEngine
+
+    cfg = ESConfig(pop_per_gpu=C.FLOOR_POP, horizon=C.STEP_HORIZON)
+    assert cfg.seed == C.FLOOR_SEED
+    eng = ESEngine(cfg, ctx=None, device=_dev())
+    state = eng.state_dict()
+    state.update({k: torch.from_numpy(v)
+                  for k, v in C.floor_obs_state().items()})
+    eng.load_state_dict(state)
+    floor_bits = np.float32(1e-2).view(np.uint32)
+    it = C.STEP_ITERATIONS[0]
+    before = _snapshot(eng, MLP_FIELDS)
+    fitness, obs_stat = ops.es_rollout_mlp(
+        eng.theta, cfg.sigma, cfg.seed, it, cfg.horizon, 0, C.FLOOR_POP,
+        eng.obs_mu, eng.obs_nu, eng.env_A, eng.env_B)
+    new, tol, flags = oracle.step_fp64(
+        before, fitness.cpu().numpy(), obs_stat.cpu().numpy(), cfg, cfg.seed,
+        it, C.NP_MLP)
+    eng.step(it)
+    after = _snapshot(eng, MLP_FIELDS)
+    # the reference variance is off the floor by more than its tolerance,
+    # below it in dims 0 and 1, above it in dims 2 and 3
+    assert not flags["obs_nu_clamp"].any()
+    assert (new["obs_nu"][:2] == oracle.C1EM2).all()
+    assert (tol["obs_nu"][:2] == 0.0).all()
+    assert (new["obs_nu"][2:] > oracle.C1EM2).all()
+    assert (after["obs_nu"][:2].view(np.uint32) == floor_bits).all(), (
+        after["obs_nu"])
+    worst = {}
+    _compare_step(("ESEngine floor", it), new, tol, flags, after, MLP_FIELDS,
+                  worst)
+    print("ESEngine on the variance floor: obs_nu %s, max err/tol per field "
+          "%s" % (after["obs_nu"], {k: round(v, 4) for k, v in worst.items()}))
+
+    # the clamp, reached through the engine's normaliser
+    h = S.CLAMP_STEP_H
+    inp = [t.unsqueeze(0).contiguous() for t in (
+        eng.theta, eng.obs_mu, eng.obs_nu, eng.env_A, eng.env_B)]
+    runs = {}
+    for hor in (h, h + 1):
+        _scores, _bc, final, ep = ops.es_eval_bc(
+            *inp, cfg.seed, it + 1, hor, return_final_states=True,
+            return_episodes=True)
+        runs[hor] = (final[0, 0].cpu().numpy(), ep[0, 0].cpu().numpy())
+    args = (rollout_oracle.make_policy(after["theta"]), after["obs_mu"],
+            after["obs_nu"], eng.env_A.cpu().numpy(),
+            eng.env_B.cpu().numpy())
+    st = S.one_step(args, runs[h][0])
+    sm = S.match_states(st, runs[h + 1][0])
+    s_max = max(float(np.abs(f).max()) for f, _e in runs.values())
+    err, rtol = S.match_reward(st, sm, runs[h][1], runs[h + 1][1], h, s_max)
+    hi, lo, mixed, hi_share, lo_share = S.clamp_condition(st.x_raw)
+    print("one step from h=%d: decided %.3f, state max err/tol %.3f, reward "
+          "max err/tol %.3f, x above +5 per dim %s, below -5 %s"
+          % (h, st.decided.mean(), sm.ratio.max(), (err / rtol).max(),
+             np.round(hi_share, 3), np.round(lo_share, 3)))
+    assert st.decided.mean() >= S.CAP
+    assert sm.ok.all(), np.flatnonzero(~sm.ok).tolist()
+    assert (err <= rtol).all(), np.flatnonzero(err > rtol).tolist()
+    # the clamp was reached in the floored dims, and lanes of the same
+    # operand stayed inside it
+    assert (np.abs(st.x_raw[:, :2]) > 5.0).any()
+    assert mixed

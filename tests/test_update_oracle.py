@@ -300,6 +300,34 @@ def test_obs_nu_clamp_is_flagged_and_exact_below():
     assert new["obs_nu"][0] == oracle.C1EM2 and tol["obs_nu"][0] == 0.0
 
 
+def test_floor_state_puts_dims_0_and_1_under_the_floor():
+    """The state that tests/gpu/test_update_oracle_gpu.py loads for its
+    variance-floor case, chosen here from step_fp64 with stand-in
+    statistics (every action +1, every action -1): after the step the
+    variance of dims 0 and 1 is below 1e-2 by more than its tolerance, so
+    obs_nu is the floor itself with tolerance 0, and dims 2 and 3 are
+    above it by more than theirs."""
+    state, fitness, _stat = _step_inputs()
+    state = dict(state)
+    state.update(C.floor_obs_state())
+    assert float(state["obs_count"][0]) + C.FLOOR_POP * 64 * 2 < 2.0 ** 24
+    for asign in (1.0, -1.0):
+        obs_stat = C.floor_standin_obs_stat(asign, STEP_ITER)
+        new, tol, flags = oracle.step_fp64(state, fitness, obs_stat, Cfg(),
+                                           C.FLOOR_SEED, STEP_ITER, C.NP_MLP)
+        cnt = new["obs_count"][0]
+        var = new["obs_sumsq"] / cnt - new["obs_mu"] ** 2
+        print("actions %+d: variance after the step %s" % (asign, var))
+        assert not flags["obs_nu_clamp"].any()
+        assert (var[:2] < 0.2 * oracle.C1EM2).all() and (var[2:] > 0.5).all()
+        assert (new["obs_nu"][:2] == oracle.C1EM2).all()
+        assert (tol["obs_nu"][:2] == 0.0).all()
+        assert (new["obs_nu"][2:] > oracle.C1EM2).all()
+        assert (tol["obs_nu"][2:] > 0.0).all()
+        # rstd = 9.95: a state 0.51 from the mean is clamped
+        assert abs(1.0 / np.sqrt(oracle.C1EM2 + 1e-4) - 9.95) < 0.01
+
+
 def test_step_mutations_stand_out():
     state, fitness, obs_stat = _step_inputs()
     base, tol, _flags = _step(state, fitness, obs_stat)

@@ -121,3 +121,49 @@ STEP_HORIZON = 2
 CONV_STEP_POP = 8
 POPULATION_SEEDS = (1234, 77)
 POPULATION_POP = 128
+
+
+# ---- the variance floor taken by a real step ------------------------------------
+# A running normaliser with a long history (2^23 observations; the count
+# stays exact in fp32 after the step's 128 * 64 * 2 more) whose dims 0 and 1
+# have the variance 1e-3: the step adds states of variance near 0.1, which
+# moves it to about 1.2e-3, far under the 1e-2 floor of ESEngine.step, while
+# dims 2 and 3 stay near 1.  The means differ per dim and in sign so that
+# the floored dims reach the +-5 clamp of the normalised obs on both sides.
+FLOOR_POP = 128
+FLOOR_COUNT = 2.0 ** 23
+FLOOR_MEAN = (0.3, -0.2, 0.1, -0.4)
+FLOOR_VAR = (1e-3, 1e-3, 1.0, 1.0)
+FLOOR_SEED = 1234               # ESConfig's default seed
+
+
+def floor_obs_state():
+    """obs_sum, obs_sumsq, obs_count (float32) to load into the engine."""
+    mean = np.array(FLOOR_MEAN, dtype=np.float64)
+    var = np.array(FLOOR_VAR, dtype=np.float64)
+    return {
+        "obs_sum": (FLOOR_COUNT * mean).astype(np.float32),
+        "obs_sumsq": (FLOOR_COUNT * (var + mean * mean)).astype(np.float32),
+        "obs_count": np.array([FLOOR_COUNT], dtype=np.float32),
+    }
+
+
+def floor_standin_obs_stat(asign, iteration):
+    """A stand-in for the obs_stat[9] of the step's rollout, without a
+    GPU: horizon STEP_HORIZON = 2 accumulates s_0, which is the same env
+    draw for every member, and s_1 = 0.97 s_0 + 0.08 tanh(A s_0) + asign *
+    0.05 B, here with every action of every member equal to ``asign``, the
+    two extremes of what the policy can do."""
+    from fiber_amd.es import philox_ref
+    from fiber_amd.es.engine import make_env_params
+
+    assert STEP_HORIZON == 2
+    env_A, env_B = (t.double().numpy()
+                    for t in make_env_params(FLOOR_SEED, "cpu"))
+    s0 = philox_ref.env_init_state(FLOOR_SEED, iteration, 64).astype(
+        np.float64)
+    s1 = 0.97 * s0 + 0.08 * np.tanh(s0 @ env_A.T) + asign * 0.05 * env_B
+    s = np.concatenate([s0, s1])
+    return np.concatenate([FLOOR_POP * s.sum(0), FLOOR_POP * (s * s).sum(0),
+                           [FLOOR_POP * 64.0 * STEP_HORIZON]]).astype(
+                               np.float32)
