@@ -107,6 +107,13 @@ extern "C" __global__ void me_commit(const float*, const float*, int, int,
                                      const unsigned long long*, float*,
                                      float*, int*, int*, int*);
 extern "C" __global__ void me_compact(const int*, int, int*, int*);
+// GRU recurrent policy (gru_kernels.hip)
+extern "C" __global__ void es_rollout_gru(
+    const float*, float, uint32_t, uint32_t, int, int, const float*,
+    const float*, const float*, const float*, int, float*, float*, float*,
+    float*, float*);
+extern "C" __global__ void gru_policy_step(const float*, const float*,
+                                           const float*, int, float*, float*);
 // conv policy pipeline (conv_kernels.hip)
 // PATA-EC novelty kernels (poet_kernels.hip)
 extern "C" __global__ void pata_ec_codes(const float*, int, int, int, float,
@@ -361,6 +368,47 @@ static void launch_mlp_forward(uintptr_t theta, uintptr_t x, int batch,
                      (hipStream_t)stream, (const float*)theta,
                      (const float*)x, batch, (float*)logits);
   check(hipGetLastError(), "mlp_policy_forward launch");
+}
+
+// launch_rollout for the GRU policy.  final_state / final_hidden may be 0.
+static void launch_rollout_gru(uintptr_t theta, double sigma, uint32_t seed,
+                               uint32_t iter, int horizon, int member_offset,
+                               int pop_shard, uintptr_t obs_mu,
+                               uintptr_t obs_nu, uintptr_t env_A,
+                               uintptr_t env_B, int obs_mask,
+                               uintptr_t fitness, uintptr_t obs_stat_part,
+                               uintptr_t obs_stat, uintptr_t final_state,
+                               uintptr_t final_hidden, uintptr_t stream) {
+  if (pop_shard < 1)
+    throw std::runtime_error("es_rollout_gru: pop_shard must be >= 1");
+  if (horizon < 0)
+    throw std::runtime_error("es_rollout_gru: horizon must be >= 0");
+  hipLaunchKernelGGL(es_rollout_gru, dim3(pop_shard), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)theta, (float)sigma,
+                     seed, iter, horizon, member_offset,
+                     (const float*)obs_mu, (const float*)obs_nu,
+                     (const float*)env_A, (const float*)env_B, obs_mask,
+                     (float*)fitness, (float*)obs_stat_part,
+                     (float*)obs_stat, (float*)final_state,
+                     (float*)final_hidden);
+  check(hipGetLastError(), "es_rollout_gru launch");
+  hipLaunchKernelGGL(obs_stat_reduce, dim3(2 * OBS_HOST), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)obs_stat_part,
+                     pop_shard, (float*)obs_stat);
+  check(hipGetLastError(), "obs_stat_reduce launch");
+}
+
+static void launch_gru_policy_step(uintptr_t theta, uintptr_t x, uintptr_t h,
+                                   int batch, uintptr_t logits,
+                                   uintptr_t hnew, uintptr_t stream) {
+  if (batch < 1)
+    throw std::runtime_error("gru_policy_step: batch must be >= 1");
+  const int bx = (batch + ENVS_HOST - 1) / ENVS_HOST;
+  hipLaunchKernelGGL(gru_policy_step, dim3(bx), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)theta,
+                     (const float*)x, (const float*)h, batch, (float*)logits,
+                     (float*)hnew);
+  check(hipGetLastError(), "gru_policy_step launch");
 }
 
 static void launch_gemm64_probe(uintptr_t a, uintptr_t b, uintptr_t c,
@@ -1007,6 +1055,17 @@ PYBIND11_MODULE(_ops, m) {
   m.def("centered_rank_sorted", &launch_centered_rank_sorted, py::arg("f"),
         py::arg("n"), py::arg("out"), py::arg("work"),
         py::arg("work_bytes"), py::arg("stream"));
+  m.attr("GRU_NPARAMS") = 13442;
+  m.def("es_rollout_gru", &launch_rollout_gru, py::arg("theta"),
+        py::arg("sigma"), py::arg("seed"), py::arg("iter"),
+        py::arg("horizon"), py::arg("member_offset"), py::arg("pop_shard"),
+        py::arg("obs_mu"), py::arg("obs_nu"), py::arg("env_A"),
+        py::arg("env_B"), py::arg("obs_mask"), py::arg("fitness"),
+        py::arg("obs_stat_part"), py::arg("obs_stat"),
+        py::arg("final_state"), py::arg("final_hidden"), py::arg("stream"));
+  m.def("gru_policy_step", &launch_gru_policy_step, py::arg("theta"),
+        py::arg("x"), py::arg("h"), py::arg("batch"), py::arg("logits"),
+        py::arg("hnew"), py::arg("stream"));
   m.def("mlp_policy_forward", &launch_mlp_forward, py::arg("theta"),
         py::arg("x"), py::arg("batch"), py::arg("logits"),
         py::arg("stream"));

@@ -70,6 +70,18 @@ class build_ext(_build_ext):
                          "conv_kernels.hip"),
             os.path.join(ROOT, "fiber_amd", "csrc", "ops", "bindings.cpp"),
         ]
+        # GRU recurrent policy: shares es_kernels.hip's device code like the
+        # files above, but is compiled on its own with packed fp32
+        # instructions off, and joins the link as an object.  The flag is
+        # what keeps es_rollout_gru free of scratch: with packed fp32 on
+        # it spills 5 VGPRs (24 B/lane) at its 128-VGPR budget, with it off
+        # it has 128 VGPRs and none (profiles/gru.md).  A flag on the one
+        # command that compiles srcs would change every other kernel, hence
+        # the separate compile.  The object reaches the link as -Wl,<path>:
+        # named plainly next to the .hip sources, hipcc reads it as HIP
+        # source text and the build fails.
+        gru_src = os.path.join(ROOT, "fiber_amd", "csrc", "ops",
+                               "gru_kernels.hip")
         hdrs = [
             os.path.join(ROOT, "fiber_amd", "csrc", "ops", "philox.h"),
             os.path.join(ROOT, "fiber_amd", "csrc", "ops", "ga_shared.h"),
@@ -77,11 +89,12 @@ class build_ext(_build_ext):
             os.path.join(ROOT, "fiber_amd", "csrc", "ops", "me_grid.h"),
         ]
         if os.path.exists(out):
-            newest_src = max(os.path.getmtime(s) for s in srcs + hdrs)
+            newest_src = max(os.path.getmtime(s)
+                             for s in srcs + hdrs + [gru_src])
             if os.path.getmtime(out) >= newest_src:
                 print("fiber_amd._ops up to date")
                 return
-        cmd = [
+        common = [
             HIPCC,
             "--offload-arch=" + GFX_ARCH,
             "-O3",
@@ -93,6 +106,16 @@ class build_ext(_build_ext):
             "-mllvm",
             "-amdgpu-mfma-vgpr-form=1",
             "-fPIC",
+        ]
+        os.makedirs(self.build_temp, exist_ok=True)
+        gru_obj = os.path.join(self.build_temp, "gru_kernels.o")
+        gru_cmd = common + [
+            "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
+            "-c", gru_src, "-o", gru_obj,
+        ]
+        print(" ".join(gru_cmd))
+        subprocess.check_call(gru_cmd)
+        cmd = common + [
             "-shared",
             "-I",
             pybind11.get_include(),
@@ -100,7 +123,7 @@ class build_ext(_build_ext):
             os.path.join(sys.prefix, "include", "python%d.%d" % sys.version_info[:2]),
             "-I",
             "/usr/include/python%d.%d" % sys.version_info[:2],
-        ] + srcs + ["-o", out]
+        ] + srcs + ["-Wl," + gru_obj, "-o", out]
         print(" ".join(cmd))
         subprocess.check_call(cmd)
 
