@@ -109,9 +109,10 @@ def _sigmoid_slope(a, radius):
     return s * (1.0 - s)
 
 
-def cell(pol, x, h, x_slack=None, bf16=True, slip=None):
+def cell(pol, x, h, x_slack=None, bf16=True, slip=None, with_pre=False):
     """One step for ``x`` [E][4] and the carried ``h`` [E][64]:
-    ``(h', logits, tol_h, tol_logits)``.
+    ``(h', logits, tol_h, tol_logits)``; ``with_pre`` appends the gate
+    pre-activations ``(a_r, a_z, a_n)``, each [E][64].
 
     ``x_slack`` [E][4] is what the kernel's x may differ by (the bf16
     spacing where its rounding is ambiguous).  ``slip`` names a deliberate
@@ -168,6 +169,8 @@ def cell(pol, x, h, x_slack=None, bf16=True, slip=None):
     tol_l = (tol_h @ np.abs(pol.wo).T + np.abs(hn) @ pol.wo_slack.T
              + N_LOGIT * U * (np.abs(t).sum(-1) + np.abs(pol.bo))
              + pol.bo_err)
+    if with_pre:
+        return hn, logits, tol_h, tol_l, (a_r, a_z, pre)
     return hn, logits, tol_h, tol_l
 
 
@@ -203,3 +206,51 @@ def env_step(s, action, env_A, env_B):
     tol = (C008 * (EPS_TANH + drive_err)
            + U * (np.abs(p97) + np.abs(inner) + np.abs(c05b) + np.abs(snew)))
     return snew, tol
+
+
+Rollout = collections.namedtuple("Rollout", [
+    "s",        # [steps + 1][E][4]   env state, s[0] = s0
+    "h",        # [steps + 1][E][64]  carried hidden state, h[0] = 0
+    "x",        # [steps][E][4]       what the policy saw at step t
+    "x_raw",    # [steps][E][4]       normalised obs before mask and clamp
+    "pre",      # [steps][3][E][64]   gate pre-activations a_r, a_z, a_n
+    "logits",   # [steps][E][2]
+    "tol_l",    # [steps][E][2]       cell's logits tolerance at step t
+    "action"])  # [steps][E]          l1 > l0
+
+
+def rollout(pol, obs_mu, obs_nu, obs_mask, env_A, env_B, s0, steps):
+    """``observe -> cell -> env_step`` chained for ``steps`` steps from the
+    state ``s0`` [E][4] and a zero hidden state.  The state and the hidden
+    state are rounded to fp32 between steps, as the kernel holds them.
+
+    This serves only to choose test inputs and to state conditions about
+    them on the CPU (how many steps are decided, where the clamp fires,
+    how far the gates saturate).  Its tolerances are those of one step:
+    nothing here bounds the kernel over several steps, and no comparison
+    with the kernel goes through it."""
+    mu = np.asarray(obs_mu, dtype=np.float32).astype(np.float64)
+    nu = np.asarray(obs_nu, dtype=np.float32).astype(np.float64)
+    s = np.asarray(s0, dtype=np.float32)
+    h = np.zeros((s.shape[0], HID), dtype=np.float32)
+    out = {k: [] for k in Rollout._fields}
+    out["s"].append(s)
+    out["h"].append(h)
+    for _t in range(steps):
+        x, x_slack = observe(s, mu, nu, obs_mask)
+        hn, logits, _tol_h, tol_l, pre = cell(pol, x, h, x_slack,
+                                              with_pre=True)
+        action = logits[:, 1] > logits[:, 0]
+        s = env_step(s, action, env_A, env_B)[0].astype(np.float32)
+        h = hn.astype(np.float32)
+        out["x"].append(x)
+        out["x_raw"].append(
+            (out["s"][-1].astype(np.float64) - mu) / np.sqrt(nu + C1EM4))
+        out["pre"].append(np.stack(pre))
+        out["logits"].append(logits)
+        out["tol_l"].append(tol_l)
+        out["action"].append(action)
+        out["s"].append(s)
+        out["h"].append(h)
+    return Rollout(*(np.stack(out[k]) if out[k] else np.zeros((0,))
+                     for k in Rollout._fields))

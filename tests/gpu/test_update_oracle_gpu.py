@@ -59,7 +59,7 @@ def _one_hot_draws(ops, seed, iteration, pair, nparams):
 # ---- device draws ---------------------------------------------------------------
 
 @requires_gpu
-@pytest.mark.parametrize("nparams", (C.NP_CONV, C.NP_MLP))
+@pytest.mark.parametrize("nparams", (C.NP_CONV, C.NP_MLP, C.NP_GRU))
 @pytest.mark.parametrize("seed,iteration,pair", C.TRIPLES)
 def test_device_draws_within_z_side_ulps(seed, iteration, pair, nparams):
     from fiber_amd import ops
@@ -89,7 +89,8 @@ def test_grad_chunks_matches_the_binding():
     from fiber_amd import ops
 
     o = ops._require_ops()
-    for nparams in (C.NP_MLP, C.NP_CONV, 4 * 256 * 31, 4 * 256 * 31 + 1):
+    for nparams in (C.NP_MLP, C.NP_CONV, C.NP_GRU, 4 * 256 * 31,
+                    4 * 256 * 31 + 1):
         for pairs in (1, 4, 63, 64, 65, 66, 70, 1024):
             assert o.es_grad_chunks(pairs, nparams) == oracle.grad_chunks(
                 pairs, nparams), (pairs, nparams)
@@ -158,6 +159,24 @@ def test_es_grad_at_the_conv_parameter_count(begin, end):
              oracle.grad_per_chunk(end - begin, C.NP_CONV), ratio.max()))
     assert ratio.max() <= 1.0
     assert idx[-1] == C.NP_CONV - 1 and ratio[-2:].max() <= 1.0  # the tail
+
+
+@requires_gpu
+def test_es_grad_at_the_gru_parameter_count():
+    from fiber_amd import ops
+
+    begin, end = C.GRU_RANGE
+    g, _abs, tol, _j = C.grad_reference(begin, end, C.NP_GRU)
+    out = _grad(ops, begin, end, C.NP_GRU)
+    assert out.numel() == C.NP_GRU == ops.GRU_NPARAMS
+    got = _f64(out)
+    assert np.isfinite(got).all(), "a weight outside the range was read"
+    ratio = np.abs(got - g) / tol
+    print("es_grad NP_GRU pairs [%d, %d) chunks %d: max err/tol = %.4f"
+          % (begin, end, oracle.grad_chunks(end - begin, C.NP_GRU),
+             ratio.max()))
+    assert ratio.max() <= 1.0
+    assert C.NP_GRU % 4 == 2 and ratio[-2:].max() <= 1.0  # the tail of 2
 
 
 # ---- es_perturb and es_grad see the same eps --------------------------------------

@@ -10,6 +10,7 @@ from fiber_amd.es import update_oracle as oracle
 
 NP_MLP = 4610
 NP_CONV = 677686
+NP_GRU = 13442     # the GRU policy: 3360 whole blocks of 4 and a tail of 2
 
 # (seed, iteration, pair) of the draw vectors that are compared one by one
 TRIPLES = ((1234, 3, 5), (7, 1, 0), (5, 2, 40))
@@ -39,6 +40,9 @@ SHARDS = ((6, 38), (38, 76))
 WHOLE = (6, 76)
 # at nparams = NP_CONV: one chunk; 4 x 16; 17, 17, 17, 15
 CONV_RANGES = ((2, 6), (2, 66), (2, 68))
+# at nparams = NP_GRU: the 64 pairs of RecurrentESEngine at pop 128, from
+# pair 6 on
+GRU_RANGE = (6, 70)
 
 
 def weights(begin, end):
