@@ -114,6 +114,16 @@ extern "C" __global__ void es_rollout_gru(
     float*, float*);
 extern "C" __global__ void gru_policy_step(const float*, const float*,
                                            const float*, int, float*, float*);
+// wide MLP policies (wide_kernels.hip)
+#define WIDE_DECL(H)                                                         \
+  extern "C" __global__ void es_rollout_mlp_wide_##H(                        \
+      const float*, float, uint32_t, uint32_t, int, int, const float*,       \
+      const float*, const float*, const float*, float*, float*, float*,      \
+      float*);                                                               \
+  extern "C" __global__ void mlp_policy_forward_wide_##H(                    \
+      const float*, const float*, int, float*);
+WIDE_DECL(128)
+WIDE_DECL(256)
 // conv policy pipeline (conv_kernels.hip)
 // PATA-EC novelty kernels (poet_kernels.hip)
 extern "C" __global__ void pata_ec_codes(const float*, int, int, int, float,
@@ -409,6 +419,53 @@ static void launch_gru_policy_step(uintptr_t theta, uintptr_t x, uintptr_t h,
                      (const float*)x, (const float*)h, batch, (float*)logits,
                      (float*)hnew);
   check(hipGetLastError(), "gru_policy_step launch");
+}
+
+// launch_rollout for a wide MLP policy (hidden 128 or 256).  final_state
+// may be 0.
+static void launch_rollout_wide(uintptr_t theta, int hidden, double sigma,
+                                uint32_t seed, uint32_t iter, int horizon,
+                                int member_offset, int pop_shard,
+                                uintptr_t obs_mu, uintptr_t obs_nu,
+                                uintptr_t env_A, uintptr_t env_B,
+                                uintptr_t fitness, uintptr_t obs_stat_part,
+                                uintptr_t obs_stat, uintptr_t final_state,
+                                uintptr_t stream) {
+  if (hidden != 128 && hidden != 256)
+    throw std::runtime_error("es_rollout_mlp_wide: hidden must be 128 or 256");
+  if (pop_shard < 1)
+    throw std::runtime_error("es_rollout_mlp_wide: pop_shard must be >= 1");
+  if (horizon < 0)
+    throw std::runtime_error("es_rollout_mlp_wide: horizon must be >= 0");
+  hipLaunchKernelGGL(
+      hidden == 128 ? es_rollout_mlp_wide_128 : es_rollout_mlp_wide_256,
+      dim3(pop_shard), dim3(512), 0, (hipStream_t)stream,
+      (const float*)theta, (float)sigma, seed, iter, horizon, member_offset,
+      (const float*)obs_mu, (const float*)obs_nu, (const float*)env_A,
+      (const float*)env_B, (float*)fitness, (float*)obs_stat_part,
+      (float*)obs_stat, (float*)final_state);
+  check(hipGetLastError(), "es_rollout_mlp_wide launch");
+  hipLaunchKernelGGL(obs_stat_reduce, dim3(2 * OBS_HOST), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)obs_stat_part,
+                     pop_shard, (float*)obs_stat);
+  check(hipGetLastError(), "obs_stat_reduce launch");
+}
+
+static void launch_mlp_forward_wide(uintptr_t theta, int hidden, uintptr_t x,
+                                    int batch, uintptr_t logits,
+                                    uintptr_t stream) {
+  if (hidden != 128 && hidden != 256)
+    throw std::runtime_error(
+        "mlp_policy_forward_wide: hidden must be 128 or 256");
+  if (batch < 1)
+    throw std::runtime_error("mlp_policy_forward_wide: batch must be >= 1");
+  const int bx = (batch + ENVS_HOST - 1) / ENVS_HOST;
+  hipLaunchKernelGGL(
+      hidden == 128 ? mlp_policy_forward_wide_128
+                    : mlp_policy_forward_wide_256,
+      dim3(bx), dim3(512), 0, (hipStream_t)stream, (const float*)theta,
+      (const float*)x, batch, (float*)logits);
+  check(hipGetLastError(), "mlp_policy_forward_wide launch");
 }
 
 static void launch_gemm64_probe(uintptr_t a, uintptr_t b, uintptr_t c,
@@ -1066,6 +1123,16 @@ PYBIND11_MODULE(_ops, m) {
   m.def("gru_policy_step", &launch_gru_policy_step, py::arg("theta"),
         py::arg("x"), py::arg("h"), py::arg("batch"), py::arg("logits"),
         py::arg("hnew"), py::arg("stream"));
+  m.def("es_rollout_mlp_wide", &launch_rollout_wide, py::arg("theta"),
+        py::arg("hidden"), py::arg("sigma"), py::arg("seed"),
+        py::arg("iter"), py::arg("horizon"), py::arg("member_offset"),
+        py::arg("pop_shard"), py::arg("obs_mu"), py::arg("obs_nu"),
+        py::arg("env_A"), py::arg("env_B"), py::arg("fitness"),
+        py::arg("obs_stat_part"), py::arg("obs_stat"),
+        py::arg("final_state"), py::arg("stream"));
+  m.def("mlp_policy_forward_wide", &launch_mlp_forward_wide,
+        py::arg("theta"), py::arg("hidden"), py::arg("x"), py::arg("batch"),
+        py::arg("logits"), py::arg("stream"));
   m.def("mlp_policy_forward", &launch_mlp_forward, py::arg("theta"),
         py::arg("x"), py::arg("batch"), py::arg("logits"),
         py::arg("stream"));

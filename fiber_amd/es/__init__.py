@@ -12,6 +12,7 @@ from .population import ESPopulation  # noqa: F401
 from .recurrent import RecurrentESEngine, init_theta_gru  # noqa: F401
 from .safe_ga import SafeGAConfig, SafeGAEngine  # noqa: F401
 from .snes import SNESConfig, SNESEngine  # noqa: F401
+from .wide import WideESEngine, init_theta_wide  # noqa: F401
 from .poet import (  # noqa: F401
     apply_transfers,
     minimal_criterion,

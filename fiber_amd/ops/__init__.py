@@ -1760,5 +1760,134 @@ def gru_policy_step(theta, x, h, out=None):
     return out[0], out[1]
 
 
+# ---------------------------------------------------------------------------
+# Wide MLP policies, hidden 128 / 256 (wide_kernels.hip)
+# ---------------------------------------------------------------------------
+
+WIDE_HIDDEN = (128, 256)
+
+
+def wide_nparams(hidden):
+    """Length of the flat theta of a 4 -> hidden -> hidden -> 2 policy:
+    ``W1[H][4], b1[H], W2[H][H], b2[H], W3[2][H], b3[2]``."""
+    hidden = int(hidden)
+    if hidden == HIDDEN:
+        raise ValueError("hidden = %d is the es_rollout_mlp / "
+                         "mlp_policy_forward policy; the wide ops take %s"
+                         % (HIDDEN, list(WIDE_HIDDEN)))
+    if hidden not in WIDE_HIDDEN:
+        raise ValueError("hidden must be one of %s, got %d"
+                         % (list(WIDE_HIDDEN), hidden))
+    return hidden * hidden + 8 * hidden + 2
+
+
+def _check_wide_on(named, anchor, hidden):
+    n = wide_nparams(hidden)
+    for name, t in named:
+        _check(t, name)
+        if t.device != anchor.device:
+            raise TypeError("%s is on %s, theta on %s"
+                            % (name, t.device, anchor.device))
+    if tuple(anchor.shape) != (n,):
+        raise ValueError("theta must be [%d] for hidden = %d, got %s"
+                         % (n, hidden, tuple(anchor.shape)))
+    if anchor.data_ptr() % 16:
+        # the kernels read theta as 16-byte Philox blocks
+        raise ValueError("theta must be 16-byte aligned")
+    return n
+
+
+def es_rollout_mlp_wide(theta, hidden, sigma, seed, iteration, horizon,
+                        member_offset, pop_shard, obs_mu, obs_nu, env_A,
+                        env_B, return_final=False):
+    """``es_rollout_mlp`` for a 4 -> hidden -> hidden -> 2 policy with
+    ``hidden`` in ``WIDE_HIDDEN`` (``theta[wide_nparams(hidden)]``): one
+    launch rolls out ``pop_shard`` perturbed members x 64 envs for
+    ``horizon`` steps.  The noise is the ``es_rollout_mlp`` stream, so
+    ``es_grad(..., nparams=wide_nparams(hidden))`` regenerates it.
+
+    Returns ``(fitness[pop_shard], obs_stat[9])``, and with
+    ``return_final`` also ``final_state[pop_shard][64][4]``, the env state
+    after the last step.  Asking for it does not change a bit of the other
+    two.  ``horizon`` may be 0.
+
+    TypeError for dtype, device or contiguity, ValueError for shapes, an
+    unsupported ``hidden`` (64 is ``es_rollout_mlp``), an odd ``pop_shard``
+    or ``member_offset`` (antithetic pairs) or a negative ``horizon``."""
+    ops = _require_ops()
+    hidden = int(hidden)
+    _check_wide_on((("theta", theta), ("obs_mu", obs_mu), ("obs_nu", obs_nu),
+                    ("env_A", env_A), ("env_B", env_B)), theta, hidden)
+    for name, t, want in (("obs_mu", obs_mu, (OBS_DIM,)),
+                          ("obs_nu", obs_nu, (OBS_DIM,)),
+                          ("env_A", env_A, (OBS_DIM, OBS_DIM)),
+                          ("env_B", env_B, (OBS_DIM,))):
+        if tuple(t.shape) != want:
+            raise ValueError("%s must be %s, got %s"
+                             % (name, list(want), tuple(t.shape)))
+    pop_shard, member_offset = int(pop_shard), int(member_offset)
+    horizon = int(horizon)
+    if pop_shard < 2 or pop_shard % 2 or member_offset < 0 \
+            or member_offset % 2:
+        raise ValueError("pop_shard must be even and >= 2, member_offset "
+                         "even and >= 0 (antithetic pairs), got %d, %d"
+                         % (pop_shard, member_offset))
+    if horizon < 0:
+        raise ValueError("horizon must be >= 0, got %d" % horizon)
+    device = theta.device
+    fitness = torch.empty(pop_shard, dtype=torch.float32, device=device)
+    obs_stat = torch.zeros(2 * OBS_DIM + 1, dtype=torch.float32,
+                           device=device)
+    part = _partial_buffer(device, pop_shard * 2 * OBS_DIM)
+    final_state = None
+    if return_final:
+        final_state = torch.empty(pop_shard, ENVS_PER_MEMBER, OBS_DIM,
+                                  dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        ops.es_rollout_mlp_wide(
+            theta.data_ptr(), hidden, float(sigma), int(seed) & 0xFFFFFFFF,
+            int(iteration) & 0xFFFFFFFF, horizon, member_offset, pop_shard,
+            obs_mu.data_ptr(), obs_nu.data_ptr(), env_A.data_ptr(),
+            env_B.data_ptr(), fitness.data_ptr(), part.data_ptr(),
+            obs_stat.data_ptr(),
+            final_state.data_ptr() if return_final else 0, _stream())
+    if return_final:
+        return fitness, obs_stat, final_state
+    return fitness, obs_stat
+
+
+def mlp_policy_forward_wide(theta, hidden, x, out=None):
+    """``logits[b][2]`` of a wide policy for ``x[b][4]`` (already
+    normalised and clamped, as ``mlp_policy_forward`` takes it), ``b >= 1``,
+    all fp32 on one device.  Weights, ``x`` and ``h1`` are rounded to bf16;
+    ``h2`` stays fp32 as in the step loop of ``es_rollout_mlp_wide``, so
+    both form the same logits from the same ``x``.  ``out``, if given, is
+    contiguous fp32 ``[b][2]`` storage that is written and returned.
+    Everything is validated before the launch."""
+    ops = _require_ops()
+    hidden = int(hidden)
+    named = [("theta", theta), ("x", x)]
+    if out is not None:
+        named.append(("out", out))
+    _check_wide_on(named, theta, hidden)
+    if x.dim() != 2 or x.shape[1] != OBS_DIM:
+        raise ValueError("x must be [batch, %d], got %s"
+                         % (OBS_DIM, tuple(x.shape)))
+    batch = x.shape[0]
+    if batch < 1 or batch * OBS_DIM >= 2 ** 31:
+        raise ValueError("batch must be in [1, 2^31 / %d), got %d"
+                         % (OBS_DIM, batch))
+    if out is None:
+        out = torch.empty(batch, ACT_DIM, dtype=torch.float32,
+                          device=x.device)
+    elif tuple(out.shape) != (batch, ACT_DIM):
+        raise ValueError("out must be [%d, %d], got %s"
+                         % (batch, ACT_DIM, tuple(out.shape)))
+    with torch.cuda.device(x.device):
+        ops.mlp_policy_forward_wide(theta.data_ptr(), hidden, x.data_ptr(),
+                                    batch, out.data_ptr(), _stream())
+    return out
+
+
 def ops_available():
     return _OPS is not None

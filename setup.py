@@ -82,6 +82,10 @@ class build_ext(_build_ext):
         # source text and the build fails.
         gru_src = os.path.join(ROOT, "fiber_amd", "csrc", "ops",
                                "gru_kernels.hip")
+        # wide MLP policies (hidden 128 / 256): the same arrangement, and
+        # the same flag
+        wide_src = os.path.join(ROOT, "fiber_amd", "csrc", "ops",
+                                "wide_kernels.hip")
         hdrs = [
             os.path.join(ROOT, "fiber_amd", "csrc", "ops", "philox.h"),
             os.path.join(ROOT, "fiber_amd", "csrc", "ops", "ga_shared.h"),
@@ -90,7 +94,7 @@ class build_ext(_build_ext):
         ]
         if os.path.exists(out):
             newest_src = max(os.path.getmtime(s)
-                             for s in srcs + hdrs + [gru_src])
+                             for s in srcs + hdrs + [gru_src, wide_src])
             if os.path.getmtime(out) >= newest_src:
                 print("fiber_amd._ops up to date")
                 return
@@ -108,13 +112,18 @@ class build_ext(_build_ext):
             "-fPIC",
         ]
         os.makedirs(self.build_temp, exist_ok=True)
-        gru_obj = os.path.join(self.build_temp, "gru_kernels.o")
-        gru_cmd = common + [
-            "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
-            "-c", gru_src, "-o", gru_obj,
-        ]
-        print(" ".join(gru_cmd))
-        subprocess.check_call(gru_cmd)
+        objs = []
+        for src in (gru_src, wide_src):
+            obj = os.path.join(
+                self.build_temp,
+                os.path.splitext(os.path.basename(src))[0] + ".o")
+            obj_cmd = common + [
+                "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
+                "-c", src, "-o", obj,
+            ]
+            print(" ".join(obj_cmd))
+            subprocess.check_call(obj_cmd)
+            objs.append(obj)
         cmd = common + [
             "-shared",
             "-I",
@@ -123,7 +132,7 @@ class build_ext(_build_ext):
             os.path.join(sys.prefix, "include", "python%d.%d" % sys.version_info[:2]),
             "-I",
             "/usr/include/python%d.%d" % sys.version_info[:2],
-        ] + srcs + ["-Wl," + gru_obj, "-o", out]
+        ] + srcs + ["-Wl," + o for o in objs] + ["-o", out]
         print(" ".join(cmd))
         subprocess.check_call(cmd)
 
