@@ -114,6 +114,14 @@ extern "C" __global__ void es_rollout_gru(
     float*, float*);
 extern "C" __global__ void gru_policy_step(const float*, const float*,
                                            const float*, int, float*, float*);
+// LSTM recurrent policy (lstm_kernels.hip)
+extern "C" __global__ void es_rollout_lstm(
+    const float*, float, uint32_t, uint32_t, int, int, const float*,
+    const float*, const float*, const float*, int, float*, float*, float*,
+    float*, float*, float*);
+extern "C" __global__ void lstm_policy_step(const float*, const float*,
+                                            const float*, const float*, int,
+                                            float*, float*, float*);
 // wide MLP policies (wide_kernels.hip)
 #define WIDE_DECL(H)                                                         \
   extern "C" __global__ void es_rollout_mlp_wide_##H(                        \
@@ -419,6 +427,50 @@ static void launch_gru_policy_step(uintptr_t theta, uintptr_t x, uintptr_t h,
                      (const float*)x, (const float*)h, batch, (float*)logits,
                      (float*)hnew);
   check(hipGetLastError(), "gru_policy_step launch");
+}
+
+// launch_rollout for the LSTM policy: 512 threads per member.  final_state /
+// final_hidden / final_cell may be 0.
+static void launch_rollout_lstm(uintptr_t theta, double sigma, uint32_t seed,
+                                uint32_t iter, int horizon, int member_offset,
+                                int pop_shard, uintptr_t obs_mu,
+                                uintptr_t obs_nu, uintptr_t env_A,
+                                uintptr_t env_B, int obs_mask,
+                                uintptr_t fitness, uintptr_t obs_stat_part,
+                                uintptr_t obs_stat, uintptr_t final_state,
+                                uintptr_t final_hidden, uintptr_t final_cell,
+                                uintptr_t stream) {
+  if (pop_shard < 1)
+    throw std::runtime_error("es_rollout_lstm: pop_shard must be >= 1");
+  if (horizon < 0)
+    throw std::runtime_error("es_rollout_lstm: horizon must be >= 0");
+  hipLaunchKernelGGL(es_rollout_lstm, dim3(pop_shard), dim3(512), 0,
+                     (hipStream_t)stream, (const float*)theta, (float)sigma,
+                     seed, iter, horizon, member_offset,
+                     (const float*)obs_mu, (const float*)obs_nu,
+                     (const float*)env_A, (const float*)env_B, obs_mask,
+                     (float*)fitness, (float*)obs_stat_part,
+                     (float*)obs_stat, (float*)final_state,
+                     (float*)final_hidden, (float*)final_cell);
+  check(hipGetLastError(), "es_rollout_lstm launch");
+  hipLaunchKernelGGL(obs_stat_reduce, dim3(2 * OBS_HOST), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)obs_stat_part,
+                     pop_shard, (float*)obs_stat);
+  check(hipGetLastError(), "obs_stat_reduce launch");
+}
+
+static void launch_lstm_policy_step(uintptr_t theta, uintptr_t x, uintptr_t h,
+                                    uintptr_t c, int batch, uintptr_t logits,
+                                    uintptr_t hnew, uintptr_t cnew,
+                                    uintptr_t stream) {
+  if (batch < 1)
+    throw std::runtime_error("lstm_policy_step: batch must be >= 1");
+  const int bx = (batch + ENVS_HOST - 1) / ENVS_HOST;
+  hipLaunchKernelGGL(lstm_policy_step, dim3(bx), dim3(512), 0,
+                     (hipStream_t)stream, (const float*)theta,
+                     (const float*)x, (const float*)h, (const float*)c, batch,
+                     (float*)logits, (float*)hnew, (float*)cnew);
+  check(hipGetLastError(), "lstm_policy_step launch");
 }
 
 // launch_rollout for a wide MLP policy (hidden 128 or 256).  final_state
@@ -1123,6 +1175,19 @@ PYBIND11_MODULE(_ops, m) {
   m.def("gru_policy_step", &launch_gru_policy_step, py::arg("theta"),
         py::arg("x"), py::arg("h"), py::arg("batch"), py::arg("logits"),
         py::arg("hnew"), py::arg("stream"));
+  m.attr("LSTM_NPARAMS") = 17794;
+  m.def("es_rollout_lstm", &launch_rollout_lstm, py::arg("theta"),
+        py::arg("sigma"), py::arg("seed"), py::arg("iter"),
+        py::arg("horizon"), py::arg("member_offset"), py::arg("pop_shard"),
+        py::arg("obs_mu"), py::arg("obs_nu"), py::arg("env_A"),
+        py::arg("env_B"), py::arg("obs_mask"), py::arg("fitness"),
+        py::arg("obs_stat_part"), py::arg("obs_stat"),
+        py::arg("final_state"), py::arg("final_hidden"),
+        py::arg("final_cell"), py::arg("stream"));
+  m.def("lstm_policy_step", &launch_lstm_policy_step, py::arg("theta"),
+        py::arg("x"), py::arg("h"), py::arg("c"), py::arg("batch"),
+        py::arg("logits"), py::arg("hnew"), py::arg("cnew"),
+        py::arg("stream"));
   m.def("es_rollout_mlp_wide", &launch_rollout_wide, py::arg("theta"),
         py::arg("hidden"), py::arg("sigma"), py::arg("seed"),
         py::arg("iter"), py::arg("horizon"), py::arg("member_offset"),

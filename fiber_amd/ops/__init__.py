@@ -1889,5 +1889,136 @@ def mlp_policy_forward_wide(theta, hidden, x, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------
+# LSTM recurrent policy (lstm_kernels.hip)
+# ---------------------------------------------------------------------------
+
+LSTM_NPARAMS = _OPS.LSTM_NPARAMS if _OPS else 17794
+
+
+def _check_lstm_on(named, anchor):
+    for name, t in named:
+        _check(t, name)
+        if t.device != anchor.device:
+            raise TypeError("%s is on %s, theta on %s"
+                            % (name, t.device, anchor.device))
+    if tuple(anchor.shape) != (LSTM_NPARAMS,):
+        raise ValueError("theta must be [%d], got %s"
+                         % (LSTM_NPARAMS, tuple(anchor.shape)))
+    if anchor.data_ptr() % 16:
+        # the kernels read theta as 16-byte Philox blocks
+        raise ValueError("theta must be 16-byte aligned")
+
+
+def es_rollout_lstm(theta, sigma, seed, iteration, horizon, member_offset,
+                    pop_shard, obs_mu, obs_nu, env_A, env_B, obs_mask=0b1111,
+                    return_final=False):
+    """``es_rollout_gru`` for the LSTM policy (``theta[LSTM_NPARAMS]``,
+    torch.nn.LSTMCell's gate order i, f, g, o): one launch rolls out
+    ``pop_shard`` perturbed members x 64 envs for ``horizon`` steps, the
+    hidden and the cell state starting at zero.  Bit ``d`` of ``obs_mask``
+    says that observation dim ``d`` is visible; a hidden dim reaches the
+    policy as 0 (the observation statistics still count it).
+
+    Returns ``(fitness[pop_shard], obs_stat[9])``, and with
+    ``return_final`` also ``final_state[pop_shard][64][4]``,
+    ``final_hidden[pop_shard][64][64]`` (the fp32 ``h'`` that the last
+    logits were read from) and ``final_cell[pop_shard][64][64]`` (the
+    carried fp32 cell state).  Asking for them does not change a bit of the
+    other two.  ``horizon`` may be 0.
+
+    TypeError for dtype, device or contiguity, ValueError for shapes, an odd
+    ``pop_shard`` or ``member_offset`` (antithetic pairs), ``horizon`` or
+    ``obs_mask`` out of range."""
+    ops = _require_ops()
+    _check_lstm_on((("theta", theta), ("obs_mu", obs_mu), ("obs_nu", obs_nu),
+                    ("env_A", env_A), ("env_B", env_B)), theta)
+    for name, t, want in (("obs_mu", obs_mu, (OBS_DIM,)),
+                          ("obs_nu", obs_nu, (OBS_DIM,)),
+                          ("env_A", env_A, (OBS_DIM, OBS_DIM)),
+                          ("env_B", env_B, (OBS_DIM,))):
+        if tuple(t.shape) != want:
+            raise ValueError("%s must be %s, got %s"
+                             % (name, list(want), tuple(t.shape)))
+    pop_shard, member_offset = int(pop_shard), int(member_offset)
+    horizon, obs_mask = int(horizon), int(obs_mask)
+    if pop_shard < 2 or pop_shard % 2 or member_offset < 0 \
+            or member_offset % 2:
+        raise ValueError("pop_shard must be even and >= 2, member_offset "
+                         "even and >= 0 (antithetic pairs), got %d, %d"
+                         % (pop_shard, member_offset))
+    if horizon < 0:
+        raise ValueError("horizon must be >= 0, got %d" % horizon)
+    if not 0 <= obs_mask < 2 ** OBS_DIM:
+        raise ValueError("obs_mask must be in [0, %d), got %d"
+                         % (2 ** OBS_DIM, obs_mask))
+    device = theta.device
+    fitness = torch.empty(pop_shard, dtype=torch.float32, device=device)
+    obs_stat = torch.zeros(2 * OBS_DIM + 1, dtype=torch.float32,
+                           device=device)
+    part = _partial_buffer(device, pop_shard * 2 * OBS_DIM)
+    final = ()
+    if return_final:
+        final = tuple(
+            torch.empty(pop_shard, ENVS_PER_MEMBER, n, dtype=torch.float32,
+                        device=device) for n in (OBS_DIM, HIDDEN, HIDDEN))
+    with torch.cuda.device(device):
+        ops.es_rollout_lstm(
+            theta.data_ptr(), float(sigma), int(seed) & 0xFFFFFFFF,
+            int(iteration) & 0xFFFFFFFF, horizon, member_offset, pop_shard,
+            obs_mu.data_ptr(), obs_nu.data_ptr(), env_A.data_ptr(),
+            env_B.data_ptr(), obs_mask, fitness.data_ptr(), part.data_ptr(),
+            obs_stat.data_ptr(),
+            *([t.data_ptr() for t in final] or [0, 0, 0]), _stream())
+    return (fitness, obs_stat) + final
+
+
+def lstm_policy_step(theta, x, h, c, out=None):
+    """One step of the LSTM policy on the MFMA path: ``(logits[b][2],
+    hnew[b][64], cnew[b][64])`` for ``x[b][4]`` (already normalised, as
+    ``mlp_policy_forward`` takes it) and the carried ``h[b][64]`` and
+    ``c[b][64]``, all fp32 on one device, ``b >= 1``.  Weights, ``x`` and
+    the ``h`` the matmul reads are rounded to bf16; ``c``, ``cnew``,
+    ``hnew`` and the logits formed from it are fp32, as in
+    ``es_rollout_lstm``.  ``out``, if given, is a triple of contiguous fp32
+    tensors ``(logits, hnew, cnew)`` that are written and returned.  The
+    kernel moves the states as 16-byte vectors: ``h``, ``c``, ``hnew`` and
+    ``cnew`` must start on a 16-byte boundary.  Everything is validated
+    before the launch."""
+    ops = _require_ops()
+    named = [("theta", theta), ("x", x), ("h", h), ("c", c)]
+    if out is not None:
+        named += [("out[%d]" % i, t) for i, t in enumerate(out)]
+    _check_lstm_on(named, theta)
+    if x.dim() != 2 or x.shape[1] != OBS_DIM:
+        raise ValueError("x must be [batch, %d], got %s"
+                         % (OBS_DIM, tuple(x.shape)))
+    batch = x.shape[0]
+    if batch < 1 or batch * HIDDEN >= 2 ** 31:
+        raise ValueError("batch must be in [1, 2^31 / %d), got %d"
+                         % (HIDDEN, batch))
+    for name, t in (("h", h), ("c", c)):
+        if tuple(t.shape) != (batch, HIDDEN):
+            raise ValueError("%s must be [%d, %d], got %s"
+                             % (name, batch, HIDDEN, tuple(t.shape)))
+    if out is None:
+        out = tuple(torch.empty(batch, n, dtype=torch.float32,
+                                device=x.device)
+                    for n in (ACT_DIM, HIDDEN, HIDDEN))
+    elif [tuple(t.shape) for t in out] != [(batch, ACT_DIM), (batch, HIDDEN),
+                                           (batch, HIDDEN)]:
+        raise ValueError("out must be ([%d, %d], [%d, %d], [%d, %d])"
+                         % (batch, ACT_DIM, batch, HIDDEN, batch, HIDDEN))
+    for name, t in (("h", h), ("c", c), ("out[1]", out[1]),
+                    ("out[2]", out[2])):
+        if t.data_ptr() % 16:
+            raise ValueError("%s must be 16-byte aligned" % name)
+    with torch.cuda.device(x.device):
+        ops.lstm_policy_step(theta.data_ptr(), x.data_ptr(), h.data_ptr(),
+                             c.data_ptr(), batch, out[0].data_ptr(),
+                             out[1].data_ptr(), out[2].data_ptr(), _stream())
+    return out[0], out[1], out[2]
+
+
 def ops_available():
     return _OPS is not None

@@ -68,6 +68,13 @@ class build_ext(_build_ext):
                          "poet_kernels.hip"),
             os.path.join(ROOT, "fiber_amd", "csrc", "ops",
                          "conv_kernels.hip"),
+            # LSTM recurrent policy: a translation unit of its own like the
+            # files above.  Unlike the GRU and wide files below it needs no
+            # flag of its own: on this command es_rollout_lstm has 128 VGPRs
+            # and no scratch, with packed fp32 off it spills
+            # (profiles/lstm.md)
+            os.path.join(ROOT, "fiber_amd", "csrc", "ops",
+                         "lstm_kernels.hip"),
             os.path.join(ROOT, "fiber_amd", "csrc", "ops", "bindings.cpp"),
         ]
         # GRU recurrent policy: shares es_kernels.hip's device code like the
