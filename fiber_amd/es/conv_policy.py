@@ -14,6 +14,7 @@ import dataclasses
 import torch
 
 from .. import ops, tracing
+from . import _core
 from .engine import make_env_params
 
 
@@ -263,12 +264,8 @@ class ConvESEngine:
         grad /= float(self.pop_total) * cfg.sigma
 
         self.t_step += 1
-        b1, b2 = cfg.adam_beta1, cfg.adam_beta2
-        self.adam_m.mul_(b1).add_(grad, alpha=1 - b1)
-        self.adam_v.mul_(b2).addcmul_(grad, grad, value=1 - b2)
-        mhat = self.adam_m / (1 - b1 ** self.t_step)
-        vhat = self.adam_v / (1 - b2 ** self.t_step)
-        self.theta.add_(cfg.lr * mhat / (vhat.sqrt() + cfg.adam_eps))
+        _core.adam_ascent(self.theta, self.adam_m, self.adam_v, grad,
+                          self.t_step, cfg)
 
         return {
             "fitness_mean": float(fitness_all.mean()),

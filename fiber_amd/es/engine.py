@@ -20,6 +20,8 @@ import dataclasses
 import torch
 
 from .. import ops, tracing
+from . import _core
+from ._core import make_env_params  # noqa: F401  (its public home is here)
 
 
 @dataclasses.dataclass
@@ -39,14 +41,6 @@ class ESConfig:
     envs_per_member: int = ops.ENVS_PER_MEMBER
 
 
-def make_env_params(seed, device):
-    """Fixed synthetic-env dynamics, identical on every rank."""
-    gen = torch.Generator().manual_seed(seed ^ 0xE17)
-    env_A = (torch.randn(4, 4, generator=gen) * 0.5).to(device)
-    env_B = torch.randn(4, generator=gen).to(device)
-    return env_A.contiguous(), env_B.contiguous()
-
-
 def init_theta(seed, device):
     gen = torch.Generator().manual_seed(seed)
     theta = torch.zeros(ops.NPARAMS)
@@ -60,7 +54,7 @@ def init_theta(seed, device):
     return theta.to(device).contiguous()
 
 
-class ESEngine:
+class ESEngine(_core.ObsNormaliser):
     def __init__(self, config: ESConfig, ctx=None, device=None,
                  env_params=None):
         self.cfg = config
@@ -79,29 +73,9 @@ class ESEngine:
         self.adam_v = torch.zeros_like(self.theta)
         self.t_step = 0
 
-        # env_params = (env_A[4][4], env_B[4]) puts the engine on a given
-        # environment (a POET pair); the default is the one derived from
-        # the seed.  The environment is not part of state_dict().
-        if env_params is None:
-            self.env_A, self.env_B = make_env_params(config.seed, device)
-        else:
-            env_A, env_B = env_params
-            n = config.obs_dim
-            if tuple(env_A.shape) != (n, n) or tuple(env_B.shape) != (n,):
-                raise ValueError(
-                    "env_params must be (env_A[%d][%d], env_B[%d])"
-                    % (n, n, n))
-            # own copies: mutating the caller's tensors later must not
-            # move this engine's environment
-            self.env_A = env_A.detach().to(
-                device=device, dtype=torch.float32, copy=True).contiguous()
-            self.env_B = env_B.detach().to(
-                device=device, dtype=torch.float32, copy=True).contiguous()
-        self.obs_sum = torch.zeros(config.obs_dim, device=device)
-        self.obs_sumsq = torch.zeros(config.obs_dim, device=device)
-        self.obs_count = torch.zeros(1, device=device)
-        self.obs_mu = torch.zeros(config.obs_dim, device=device)
-        self.obs_nu = torch.ones(config.obs_dim, device=device)
+        self.env_A, self.env_B = _core.resolve_env(config, device,
+                                                   env_params)
+        self._init_normaliser()
 
         # static workspace so repeated steps allocate nothing
         self._fitness_all = torch.empty(self.pop_total, device=device)
@@ -156,21 +130,11 @@ class ESEngine:
 
         # maximize fitness => ascend
         self.t_step += 1
-        b1, b2 = cfg.adam_beta1, cfg.adam_beta2
-        self.adam_m.mul_(b1).add_(grad, alpha=1 - b1)
-        self.adam_v.mul_(b2).addcmul_(grad, grad, value=1 - b2)
-        mhat = self.adam_m / (1 - b1 ** self.t_step)
-        vhat = self.adam_v / (1 - b2 ** self.t_step)
-        self.theta.add_(cfg.lr * mhat / (vhat.sqrt() + cfg.adam_eps))
+        _core.adam_ascent(self.theta, self.adam_m, self.adam_v, grad,
+                          self.t_step, cfg)
 
         # running obs normalization (applied next iteration)
-        self.obs_sum += obs_stat[: cfg.obs_dim]
-        self.obs_sumsq += obs_stat[cfg.obs_dim : 2 * cfg.obs_dim]
-        self.obs_count += obs_stat[2 * cfg.obs_dim]
-        count = self.obs_count.clamp_min(1.0)
-        self.obs_mu = (self.obs_sum / count).contiguous()
-        var = self.obs_sumsq / count - self.obs_mu ** 2
-        self.obs_nu = var.clamp_min(1e-2).contiguous()
+        self._merge_obs_stat(obs_stat)
 
         return {
             "fitness_mean": float(fitness_all.mean()),
@@ -216,20 +180,8 @@ class ESEngine:
         where ``|l1 - l0|`` is under ``sum_i |w3[1][i] - w3[0][i]| *
         spacing(h2_i) / 2`` the two may choose differently
         (profiles/forward_oracle.md)."""
-        if not torch.is_tensor(obs):
-            raise TypeError("obs must be a tensor, got %s"
-                            % type(obs).__name__)
-        if obs.dim() != 2 or obs.shape[1] != self.cfg.obs_dim:
-            raise ValueError("obs must be [n, %d], got %s"
-                             % (self.cfg.obs_dim, tuple(obs.shape)))
-        if obs.dtype != torch.float32:
-            raise TypeError("obs must be torch.float32, got %s" % obs.dtype)
-        if obs.device != self.theta.device:
-            raise TypeError("obs is on %s, the engine on %s"
-                            % (obs.device, self.theta.device))
-        rstd = torch.rsqrt(self.obs_nu + 1e-4)
-        x = ((obs - self.obs_mu) * rstd).clamp_(-5.0, 5.0).contiguous()
-        logits = ops.mlp_policy_forward(self.theta, x)
+        logits = ops.mlp_policy_forward(self.theta,
+                                        _core.act_input(self, obs))
         actions = (logits[:, 1] > logits[:, 0]).to(torch.int64)
         if return_logits:
             return actions, logits
@@ -243,9 +195,7 @@ class ESEngine:
             "adam_m": self.adam_m.cpu(),
             "adam_v": self.adam_v.cpu(),
             "t_step": self.t_step,
-            "obs_sum": self.obs_sum.cpu(),
-            "obs_sumsq": self.obs_sumsq.cpu(),
-            "obs_count": self.obs_count.cpu(),
+            **self._obs_state(),
             "config": dataclasses.asdict(self.cfg),
         }
 
@@ -254,23 +204,9 @@ class ESEngine:
         self.adam_m.copy_(state["adam_m"].to(self.device))
         self.adam_v.copy_(state["adam_v"].to(self.device))
         self.t_step = int(state["t_step"])
-        self.obs_sum.copy_(state["obs_sum"].to(self.device))
-        self.obs_sumsq.copy_(state["obs_sumsq"].to(self.device))
-        self.obs_count.copy_(state["obs_count"].to(self.device))
-        count = self.obs_count.clamp_min(1.0)
-        self.obs_mu = (self.obs_sum / count).contiguous()
-        var = self.obs_sumsq / count - self.obs_mu ** 2
-        self.obs_nu = var.clamp_min(1e-2).contiguous()
+        self._load_obs_state(state)
 
-    def save(self, path):
-        import torch as _torch
-
-        _torch.save(self.state_dict(), path)
-
-    def load(self, path):
-        import torch as _torch
-
-        self.load_state_dict(_torch.load(path, weights_only=False))
+    save, load = _core.save, _core.load
 
 
 # ---------------------------------------------------------------------------

@@ -47,7 +47,8 @@ import numpy as np
 import torch
 
 from .. import ops, tracing
-from .engine import init_theta, make_env_params
+from . import _core
+from .engine import init_theta
 
 
 @dataclasses.dataclass
@@ -87,7 +88,7 @@ class GAConfig:
                              % self.sigma)
 
 
-class GAEngine:
+class GAEngine(_core.ObsNormaliser):
     def __init__(self, config: GAConfig, ctx=None, device=None,
                  env_params=None):
         if ctx is not None:
@@ -107,26 +108,9 @@ class GAEngine:
                                   device=device)
         self.generation = 0
 
-        # env_params = (env_A[4][4], env_B[4]) as for ESEngine; not part of
-        # state_dict().
-        if env_params is None:
-            self.env_A, self.env_B = make_env_params(config.seed, device)
-        else:
-            env_A, env_B = env_params
-            n = config.obs_dim
-            if tuple(env_A.shape) != (n, n) or tuple(env_B.shape) != (n,):
-                raise ValueError(
-                    "env_params must be (env_A[%d][%d], env_B[%d])"
-                    % (n, n, n))
-            self.env_A = env_A.detach().to(
-                device=device, dtype=torch.float32, copy=True).contiguous()
-            self.env_B = env_B.detach().to(
-                device=device, dtype=torch.float32, copy=True).contiguous()
-        self.obs_sum = torch.zeros(config.obs_dim, device=device)
-        self.obs_sumsq = torch.zeros(config.obs_dim, device=device)
-        self.obs_count = torch.zeros(1, device=device)
-        self.obs_mu = torch.zeros(config.obs_dim, device=device)
-        self.obs_nu = torch.ones(config.obs_dim, device=device)
+        self.env_A, self.env_B = _core.resolve_env(config, device,
+                                                   env_params)
+        self._init_normaliser()
 
         # what the last step launched and chose, for inspection and tests
         self.last = None
@@ -173,13 +157,7 @@ class GAEngine:
                      "slot": slot, "order": order}
 
         # running obs normalization (applied next generation)
-        self.obs_sum += obs_stat[: cfg.obs_dim]
-        self.obs_sumsq += obs_stat[cfg.obs_dim : 2 * cfg.obs_dim]
-        self.obs_count += obs_stat[2 * cfg.obs_dim]
-        count = self.obs_count.clamp_min(1.0)
-        self.obs_mu = (self.obs_sum / count).contiguous()
-        var = self.obs_sumsq / count - self.obs_mu ** 2
-        self.obs_nu = var.clamp_min(1e-2).contiguous()
+        self._merge_obs_stat(obs_stat)
 
         return {
             "fitness_mean": float(fitness.mean()),
@@ -244,9 +222,7 @@ class GAEngine:
             "theta0": self.theta0.cpu(),
             "lineage": self.lineage[:, : self.generation].cpu(),
             "generation": self.generation,
-            "obs_sum": self.obs_sum.cpu(),
-            "obs_sumsq": self.obs_sumsq.cpu(),
-            "obs_count": self.obs_count.cpu(),
+            **self._obs_state(),
             "config": dataclasses.asdict(self.cfg),
         }
 
@@ -290,16 +266,6 @@ class GAEngine:
         self.lineage[:, :generation] = rows
         self.generation = generation
         self.last = None
-        self.obs_sum.copy_(state["obs_sum"].to(self.device))
-        self.obs_sumsq.copy_(state["obs_sumsq"].to(self.device))
-        self.obs_count.copy_(state["obs_count"].to(self.device))
-        count = self.obs_count.clamp_min(1.0)
-        self.obs_mu = (self.obs_sum / count).contiguous()
-        var = self.obs_sumsq / count - self.obs_mu ** 2
-        self.obs_nu = var.clamp_min(1e-2).contiguous()
+        self._load_obs_state(state)
 
-    def save(self, path):
-        torch.save(self.state_dict(), path)
-
-    def load(self, path):
-        self.load_state_dict(torch.load(path, weights_only=False))
+    save, load = _core.save, _core.load

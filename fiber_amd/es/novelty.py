@@ -32,7 +32,8 @@ import dataclasses
 import torch
 
 from .. import ops, tracing
-from .engine import ESConfig, init_theta, make_env_params
+from . import _core
+from .engine import ESConfig, init_theta
 
 MODES = ("ns", "nsr", "nsra")
 
@@ -48,7 +49,7 @@ class NoveltyConfig:
     patience: int = 10            # nsra only: stalled steps before w drops
 
 
-class NoveltyESEngine:
+class NoveltyESEngine(_core.ObsNormaliser):
     def __init__(self, config: ESConfig, novelty: NoveltyConfig = None,
                  ctx=None, device=None, env_params=None):
         if ctx is not None:
@@ -94,25 +95,10 @@ class NoveltyESEngine:
         # noise / env-init counter of the next step, over all agents
         self.iteration = 0
 
-        if env_params is None:
-            self.env_A, self.env_B = make_env_params(config.seed, device)
-        else:
-            env_A, env_B = env_params
-            n = config.obs_dim
-            if tuple(env_A.shape) != (n, n) or tuple(env_B.shape) != (n,):
-                raise ValueError(
-                    "env_params must be (env_A[%d][%d], env_B[%d])"
-                    % (n, n, n))
-            self.env_A = env_A.detach().to(
-                device=device, dtype=torch.float32, copy=True).contiguous()
-            self.env_B = env_B.detach().to(
-                device=device, dtype=torch.float32, copy=True).contiguous()
+        self.env_A, self.env_B = _core.resolve_env(config, device,
+                                                   env_params)
         # one obs normaliser shared by all agents
-        self.obs_sum = torch.zeros(config.obs_dim, device=device)
-        self.obs_sumsq = torch.zeros(config.obs_dim, device=device)
-        self.obs_count = torch.zeros(1, device=device)
-        self.obs_mu = torch.zeros(config.obs_dim, device=device)
-        self.obs_nu = torch.ones(config.obs_dim, device=device)
+        self._init_normaliser()
 
         # archive: a ring of archive_capacity rows; row total % capacity is
         # the next one written, the first min(total, capacity) are valid
@@ -193,8 +179,6 @@ class NoveltyESEngine:
         shard = cfg.pop_per_gpu
         agent = self._choose_agent()
         theta = self.thetas[agent]
-        adam_m = self.adam_m[agent]
-        adam_v = self.adam_v[agent]
 
         with tracing.range("ns.rollout"):
             fitness, obs_stat, bc = ops.es_rollout_mlp_bc(
@@ -220,22 +204,11 @@ class NoveltyESEngine:
 
         # ascend: ESEngine.step's Adam, on the chosen agent's rows
         self.t_steps[agent] += 1
-        t_step = self.t_steps[agent]
-        b1, b2 = cfg.adam_beta1, cfg.adam_beta2
-        adam_m.mul_(b1).add_(grad, alpha=1 - b1)
-        adam_v.mul_(b2).addcmul_(grad, grad, value=1 - b2)
-        mhat = adam_m / (1 - b1 ** t_step)
-        vhat = adam_v / (1 - b2 ** t_step)
-        theta.add_(cfg.lr * mhat / (vhat.sqrt() + cfg.adam_eps))
+        _core.adam_ascent(theta, self.adam_m[agent], self.adam_v[agent],
+                          grad, self.t_steps[agent], cfg)
 
         # running obs normalization (applied next iteration)
-        self.obs_sum += obs_stat[: cfg.obs_dim]
-        self.obs_sumsq += obs_stat[cfg.obs_dim : 2 * cfg.obs_dim]
-        self.obs_count += obs_stat[2 * cfg.obs_dim]
-        count = self.obs_count.clamp_min(1.0)
-        self.obs_mu = (self.obs_sum / count).contiguous()
-        var = self.obs_sumsq / count - self.obs_mu ** 2
-        self.obs_nu = var.clamp_min(1e-2).contiguous()
+        self._merge_obs_stat(obs_stat)
 
         self.iteration = iteration + 1
 
@@ -315,9 +288,7 @@ class NoveltyESEngine:
             "adam_v": self.adam_v.cpu(),
             "t_steps": list(self.t_steps),
             "iteration": self.iteration,
-            "obs_sum": self.obs_sum.cpu(),
-            "obs_sumsq": self.obs_sumsq.cpu(),
-            "obs_count": self.obs_count.cpu(),
+            **self._obs_state(),
             "archive": self.archive.cpu(),
             "archive_total": self.archive_total,
             "agent_bc": self.agent_bc.cpu(),
@@ -343,13 +314,7 @@ class NoveltyESEngine:
         self.adam_v.copy_(state["adam_v"].to(self.device))
         self.t_steps = [int(t) for t in state["t_steps"]]
         self.iteration = int(state["iteration"])
-        self.obs_sum.copy_(state["obs_sum"].to(self.device))
-        self.obs_sumsq.copy_(state["obs_sumsq"].to(self.device))
-        self.obs_count.copy_(state["obs_count"].to(self.device))
-        count = self.obs_count.clamp_min(1.0)
-        self.obs_mu = (self.obs_sum / count).contiguous()
-        var = self.obs_sumsq / count - self.obs_mu ** 2
-        self.obs_nu = var.clamp_min(1e-2).contiguous()
+        self._load_obs_state(state)
         self.archive.copy_(state["archive"].to(self.device))
         self.archive_total = int(state["archive_total"])
         self.agent_bc.copy_(state["agent_bc"].to(self.device))
@@ -358,8 +323,4 @@ class NoveltyESEngine:
         self.stall = int(state["stall"])
         self._gen.set_state(state["generator"])
 
-    def save(self, path):
-        torch.save(self.state_dict(), path)
-
-    def load(self, path):
-        self.load_state_dict(torch.load(path, weights_only=False))
+    save, load = _core.save, _core.load

@@ -21,6 +21,7 @@ import dataclasses
 import torch
 
 from .. import ops, tracing
+from . import _core
 from .engine import ESConfig, init_theta
 
 # per-pair state rows that travel with a policy in a transfer
@@ -30,16 +31,7 @@ _STATE_FIELDS = ("theta", "adam_m", "adam_v", "obs_sum", "obs_sumsq",
                  "obs_count")
 
 
-def _normaliser(obs_sum, obs_sumsq, obs_count):
-    """(obs_mu, obs_nu) from the running sums: ESEngine's formulas, row-wise
-    (obs_count is [P][1] and broadcasts over the 4 dims)."""
-    count = obs_count.clamp_min(1.0)
-    obs_mu = (obs_sum / count).contiguous()
-    var = obs_sumsq / count - obs_mu ** 2
-    return obs_mu, var.clamp_min(1e-2).contiguous()
-
-
-class ESPopulation:
+class ESPopulation(_core.ObsNormaliser):
     def __init__(self, config: ESConfig, seeds, env_params, device=None):
         """``seeds``: P ints, pair p's noise stream and initial policy
         (``config.seed`` is not used).  ``env_params``: P tuples
@@ -71,11 +63,7 @@ class ESPopulation:
         self.env_B = torch.empty(P, n, device=device)
         for p, (env_A, env_B) in enumerate(env_params):
             self.set_env(p, env_A, env_B)
-        self.obs_sum = torch.zeros(P, n, device=device)
-        self.obs_sumsq = torch.zeros(P, n, device=device)
-        self.obs_count = torch.zeros(P, 1, device=device)
-        self.obs_mu = torch.zeros(P, n, device=device)
-        self.obs_nu = torch.ones(P, n, device=device)
+        self._init_normaliser(P)
 
     def __len__(self):
         return self.P
@@ -104,20 +92,11 @@ class ESPopulation:
         # maximize fitness => ascend; the same elementwise formulas as the
         # engine, on [P][NPARAMS]
         self.t_step += 1
-        b1, b2 = cfg.adam_beta1, cfg.adam_beta2
-        self.adam_m.mul_(b1).add_(grad, alpha=1 - b1)
-        self.adam_v.mul_(b2).addcmul_(grad, grad, value=1 - b2)
-        mhat = self.adam_m / (1 - b1 ** self.t_step)
-        vhat = self.adam_v / (1 - b2 ** self.t_step)
-        self.theta.add_(cfg.lr * mhat / (vhat.sqrt() + cfg.adam_eps))
+        _core.adam_ascent(self.theta, self.adam_m, self.adam_v, grad,
+                          self.t_step, cfg)
 
         # running obs normalization (applied next iteration)
-        n = cfg.obs_dim
-        self.obs_sum += obs_stat[:, :n]
-        self.obs_sumsq += obs_stat[:, n:2 * n]
-        self.obs_count += obs_stat[:, 2 * n:]
-        self.obs_mu, self.obs_nu = _normaliser(self.obs_sum, self.obs_sumsq,
-                                               self.obs_count)
+        self._merge_obs_stat(obs_stat)
 
         return {
             "fitness_mean": fitness.mean(dim=1),
@@ -178,12 +157,8 @@ class ESPopulation:
         for d in donors:
             if not 0 <= d < self.P:
                 raise IndexError("donor %d outside 0..%d" % (d, self.P - 1))
-        n = self.cfg.obs_dim
         for env_A, env_B in env_params:
-            if tuple(env_A.shape) != (n, n) or tuple(env_B.shape) != (n,):
-                raise ValueError(
-                    "env_params must be (env_A[%d][%d], env_B[%d])"
-                    % (n, n, n))
+            _core.check_env_shapes(env_A, env_B, self.cfg.obs_dim)
         if not seeds:
             return
         src = torch.tensor(donors, device=self.device)
@@ -233,10 +208,7 @@ class ESPopulation:
 
     def set_env(self, p, env_A, env_B):
         """Replace pair p's environment (copies, like ESEngine)."""
-        n = self.cfg.obs_dim
-        if tuple(env_A.shape) != (n, n) or tuple(env_B.shape) != (n,):
-            raise ValueError("env_params must be (env_A[%d][%d], env_B[%d])"
-                             % (n, n, n))
+        _core.check_env_shapes(env_A, env_B, self.cfg.obs_dim)
         self.env_A[p].copy_(env_A.detach().to(torch.float32))
         self.env_B[p].copy_(env_B.detach().to(torch.float32))
 
@@ -271,5 +243,4 @@ class ESPopulation:
         for f in _STATE_FIELDS + ("env_A", "env_B"):
             getattr(self, f).copy_(state[f].to(self.device))
         self.t_step = int(state["t_step"])
-        self.obs_mu, self.obs_nu = _normaliser(self.obs_sum, self.obs_sumsq,
-                                               self.obs_count)
+        self._refresh_normaliser()

@@ -156,13 +156,7 @@ class SafeGAEngine(GAEngine):
                      "slot": slot, "order": order, "steps": steps}
 
         # running obs normalization (applied next generation)
-        self.obs_sum += obs_stat[: cfg.obs_dim]
-        self.obs_sumsq += obs_stat[cfg.obs_dim : 2 * cfg.obs_dim]
-        self.obs_count += obs_stat[2 * cfg.obs_dim]
-        count = self.obs_count.clamp_min(1.0)
-        self.obs_mu = (self.obs_sum / count).contiguous()
-        var = self.obs_sumsq / count - self.obs_mu ** 2
-        self.obs_nu = var.clamp_min(1e-2).contiguous()
+        self._merge_obs_stat(obs_stat)
 
         return {
             "fitness_mean": float(fitness.mean()),
@@ -257,10 +251,4 @@ class SafeGAEngine(GAEngine):
         self.lineage[:, :generation] = rows
         self.generation = generation
         self.last = None
-        self.obs_sum.copy_(state["obs_sum"].to(self.device))
-        self.obs_sumsq.copy_(state["obs_sumsq"].to(self.device))
-        self.obs_count.copy_(state["obs_count"].to(self.device))
-        count = self.obs_count.clamp_min(1.0)
-        self.obs_mu = (self.obs_sum / count).contiguous()
-        var = self.obs_sumsq / count - self.obs_mu ** 2
-        self.obs_nu = var.clamp_min(1e-2).contiguous()
+        self._load_obs_state(state)

@@ -45,6 +45,7 @@ import math
 import torch
 
 from .. import ops, tracing
+from . import _core
 from .engine import ESConfig, ESEngine
 
 
@@ -121,12 +122,8 @@ class SNESEngine(ESEngine):
 
         # maximize fitness => ascend (ESEngine.step's Adam)
         self.t_step += 1
-        b1, b2 = cfg.adam_beta1, cfg.adam_beta2
-        self.adam_m.mul_(b1).add_(grad, alpha=1 - b1)
-        self.adam_v.mul_(b2).addcmul_(grad, grad, value=1 - b2)
-        mhat = self.adam_m / (1 - b1 ** self.t_step)
-        vhat = self.adam_v / (1 - b2 ** self.t_step)
-        self.theta.add_(cfg.lr * mhat / (vhat.sqrt() + cfg.adam_eps))
+        _core.adam_ascent(self.theta, self.adam_m, self.adam_v, grad,
+                          self.t_step, cfg)
 
         # step sizes (applied next iteration)
         self.sigma.mul_(
@@ -134,13 +131,7 @@ class SNESEngine(ESEngine):
         ).clamp_(snes.sigma_min, snes.sigma_max)
 
         # running obs normalization (applied next iteration)
-        self.obs_sum += obs_stat[: cfg.obs_dim]
-        self.obs_sumsq += obs_stat[cfg.obs_dim : 2 * cfg.obs_dim]
-        self.obs_count += obs_stat[2 * cfg.obs_dim]
-        count = self.obs_count.clamp_min(1.0)
-        self.obs_mu = (self.obs_sum / count).contiguous()
-        var = self.obs_sumsq / count - self.obs_mu ** 2
-        self.obs_nu = var.clamp_min(1e-2).contiguous()
+        self._merge_obs_stat(obs_stat)
 
         return {
             "fitness_mean": float(fitness.mean()),

@@ -1639,15 +1639,60 @@ def me_compact(arch_filled, out_filled_idx=None, out_n_filled=None):
 GRU_NPARAMS = _OPS.GRU_NPARAMS if _OPS else 13442
 
 
-def _check_gru_on(named, anchor):
+def _check_policy_on(named, theta, nparams, aligned, what=""):
+    """The ``named`` tensors are fp32, contiguous and on ``theta``'s device,
+    and ``theta`` is ``[nparams]`` (``what`` words the policy it is for).
+    ``aligned``: the kernels read theta as 16-byte Philox blocks."""
     for name, t in named:
         _check(t, name)
-        if t.device != anchor.device:
+        if t.device != theta.device:
             raise TypeError("%s is on %s, theta on %s"
-                            % (name, t.device, anchor.device))
-    if tuple(anchor.shape) != (GRU_NPARAMS,):
-        raise ValueError("theta must be [%d], got %s"
-                         % (GRU_NPARAMS, tuple(anchor.shape)))
+                            % (name, t.device, theta.device))
+    if tuple(theta.shape) != (nparams,):
+        raise ValueError("theta must be [%d]%s, got %s"
+                         % (nparams, what, tuple(theta.shape)))
+    if aligned and theta.data_ptr() % 16:
+        raise ValueError("theta must be 16-byte aligned")
+
+
+def _rollout_prelude(theta, nparams, aligned, what, pop_shard, member_offset,
+                     horizon, obs_mu, obs_nu, env_A, env_B, obs_mask=None):
+    """What ``es_rollout_gru``, ``es_rollout_mlp_wide`` and
+    ``es_rollout_lstm`` do before their launch: every check, then the
+    outputs.  Returns ``(pop_shard, member_offset, horizon, obs_mask)`` as
+    ints (``obs_mask`` None where the policy has none) and ``fitness``,
+    ``obs_stat`` and the partial buffer."""
+    _check_policy_on((("theta", theta), ("obs_mu", obs_mu),
+                      ("obs_nu", obs_nu), ("env_A", env_A),
+                      ("env_B", env_B)), theta, nparams, aligned, what)
+    for name, t, want in (("obs_mu", obs_mu, (OBS_DIM,)),
+                          ("obs_nu", obs_nu, (OBS_DIM,)),
+                          ("env_A", env_A, (OBS_DIM, OBS_DIM)),
+                          ("env_B", env_B, (OBS_DIM,))):
+        if tuple(t.shape) != want:
+            raise ValueError("%s must be %s, got %s"
+                             % (name, list(want), tuple(t.shape)))
+    pop_shard, member_offset = int(pop_shard), int(member_offset)
+    horizon = int(horizon)
+    if pop_shard < 2 or pop_shard % 2 or member_offset < 0 \
+            or member_offset % 2:
+        raise ValueError("pop_shard must be even and >= 2, member_offset "
+                         "even and >= 0 (antithetic pairs), got %d, %d"
+                         % (pop_shard, member_offset))
+    if horizon < 0:
+        raise ValueError("horizon must be >= 0, got %d" % horizon)
+    if obs_mask is not None:
+        obs_mask = int(obs_mask)
+        if not 0 <= obs_mask < 2 ** OBS_DIM:
+            raise ValueError("obs_mask must be in [0, %d), got %d"
+                             % (2 ** OBS_DIM, obs_mask))
+    device = theta.device
+    fitness = torch.empty(pop_shard, dtype=torch.float32, device=device)
+    obs_stat = torch.zeros(2 * OBS_DIM + 1, dtype=torch.float32,
+                           device=device)
+    part = _partial_buffer(device, pop_shard * 2 * OBS_DIM)
+    return (pop_shard, member_offset, horizon, obs_mask, fitness, obs_stat,
+            part)
 
 
 def es_rollout_gru(theta, sigma, seed, iteration, horizon, member_offset,
@@ -1669,32 +1714,11 @@ def es_rollout_gru(theta, sigma, seed, iteration, horizon, member_offset,
     ``pop_shard`` or ``member_offset`` (antithetic pairs), ``horizon`` or
     ``obs_mask`` out of range."""
     ops = _require_ops()
-    _check_gru_on((("theta", theta), ("obs_mu", obs_mu), ("obs_nu", obs_nu),
-                   ("env_A", env_A), ("env_B", env_B)), theta)
-    for name, t, want in (("obs_mu", obs_mu, (OBS_DIM,)),
-                          ("obs_nu", obs_nu, (OBS_DIM,)),
-                          ("env_A", env_A, (OBS_DIM, OBS_DIM)),
-                          ("env_B", env_B, (OBS_DIM,))):
-        if tuple(t.shape) != want:
-            raise ValueError("%s must be %s, got %s"
-                             % (name, list(want), tuple(t.shape)))
-    pop_shard, member_offset = int(pop_shard), int(member_offset)
-    horizon, obs_mask = int(horizon), int(obs_mask)
-    if pop_shard < 2 or pop_shard % 2 or member_offset < 0 \
-            or member_offset % 2:
-        raise ValueError("pop_shard must be even and >= 2, member_offset "
-                         "even and >= 0 (antithetic pairs), got %d, %d"
-                         % (pop_shard, member_offset))
-    if horizon < 0:
-        raise ValueError("horizon must be >= 0, got %d" % horizon)
-    if not 0 <= obs_mask < 2 ** OBS_DIM:
-        raise ValueError("obs_mask must be in [0, %d), got %d"
-                         % (2 ** OBS_DIM, obs_mask))
+    (pop_shard, member_offset, horizon, obs_mask, fitness, obs_stat,
+     part) = _rollout_prelude(
+        theta, GRU_NPARAMS, False, "", pop_shard, member_offset, horizon,
+        obs_mu, obs_nu, env_A, env_B, int(obs_mask))
     device = theta.device
-    fitness = torch.empty(pop_shard, dtype=torch.float32, device=device)
-    obs_stat = torch.zeros(2 * OBS_DIM + 1, dtype=torch.float32,
-                           device=device)
-    part = _partial_buffer(device, pop_shard * 2 * OBS_DIM)
     final_state = final_hidden = None
     if return_final:
         final_state = torch.empty(pop_shard, ENVS_PER_MEMBER, OBS_DIM,
@@ -1730,7 +1754,7 @@ def gru_policy_step(theta, x, h, out=None):
     named = [("theta", theta), ("x", x), ("h", h)]
     if out is not None:
         named += [("out[0]", out[0]), ("out[1]", out[1])]
-    _check_gru_on(named, theta)
+    _check_policy_on(named, theta, GRU_NPARAMS, False)
     if x.dim() != 2 or x.shape[1] != OBS_DIM:
         raise ValueError("x must be [batch, %d], got %s"
                          % (OBS_DIM, tuple(x.shape)))
@@ -1781,22 +1805,6 @@ def wide_nparams(hidden):
     return hidden * hidden + 8 * hidden + 2
 
 
-def _check_wide_on(named, anchor, hidden):
-    n = wide_nparams(hidden)
-    for name, t in named:
-        _check(t, name)
-        if t.device != anchor.device:
-            raise TypeError("%s is on %s, theta on %s"
-                            % (name, t.device, anchor.device))
-    if tuple(anchor.shape) != (n,):
-        raise ValueError("theta must be [%d] for hidden = %d, got %s"
-                         % (n, hidden, tuple(anchor.shape)))
-    if anchor.data_ptr() % 16:
-        # the kernels read theta as 16-byte Philox blocks
-        raise ValueError("theta must be 16-byte aligned")
-    return n
-
-
 def es_rollout_mlp_wide(theta, hidden, sigma, seed, iteration, horizon,
                         member_offset, pop_shard, obs_mu, obs_nu, env_A,
                         env_B, return_final=False):
@@ -1816,29 +1824,11 @@ def es_rollout_mlp_wide(theta, hidden, sigma, seed, iteration, horizon,
     or ``member_offset`` (antithetic pairs) or a negative ``horizon``."""
     ops = _require_ops()
     hidden = int(hidden)
-    _check_wide_on((("theta", theta), ("obs_mu", obs_mu), ("obs_nu", obs_nu),
-                    ("env_A", env_A), ("env_B", env_B)), theta, hidden)
-    for name, t, want in (("obs_mu", obs_mu, (OBS_DIM,)),
-                          ("obs_nu", obs_nu, (OBS_DIM,)),
-                          ("env_A", env_A, (OBS_DIM, OBS_DIM)),
-                          ("env_B", env_B, (OBS_DIM,))):
-        if tuple(t.shape) != want:
-            raise ValueError("%s must be %s, got %s"
-                             % (name, list(want), tuple(t.shape)))
-    pop_shard, member_offset = int(pop_shard), int(member_offset)
-    horizon = int(horizon)
-    if pop_shard < 2 or pop_shard % 2 or member_offset < 0 \
-            or member_offset % 2:
-        raise ValueError("pop_shard must be even and >= 2, member_offset "
-                         "even and >= 0 (antithetic pairs), got %d, %d"
-                         % (pop_shard, member_offset))
-    if horizon < 0:
-        raise ValueError("horizon must be >= 0, got %d" % horizon)
+    (pop_shard, member_offset, horizon, _, fitness, obs_stat,
+     part) = _rollout_prelude(
+        theta, wide_nparams(hidden), True, " for hidden = %d" % hidden,
+        pop_shard, member_offset, horizon, obs_mu, obs_nu, env_A, env_B)
     device = theta.device
-    fitness = torch.empty(pop_shard, dtype=torch.float32, device=device)
-    obs_stat = torch.zeros(2 * OBS_DIM + 1, dtype=torch.float32,
-                           device=device)
-    part = _partial_buffer(device, pop_shard * 2 * OBS_DIM)
     final_state = None
     if return_final:
         final_state = torch.empty(pop_shard, ENVS_PER_MEMBER, OBS_DIM,
@@ -1869,7 +1859,8 @@ def mlp_policy_forward_wide(theta, hidden, x, out=None):
     named = [("theta", theta), ("x", x)]
     if out is not None:
         named.append(("out", out))
-    _check_wide_on(named, theta, hidden)
+    _check_policy_on(named, theta, wide_nparams(hidden), True,
+                     " for hidden = %d" % hidden)
     if x.dim() != 2 or x.shape[1] != OBS_DIM:
         raise ValueError("x must be [batch, %d], got %s"
                          % (OBS_DIM, tuple(x.shape)))
@@ -1896,20 +1887,6 @@ def mlp_policy_forward_wide(theta, hidden, x, out=None):
 LSTM_NPARAMS = _OPS.LSTM_NPARAMS if _OPS else 17794
 
 
-def _check_lstm_on(named, anchor):
-    for name, t in named:
-        _check(t, name)
-        if t.device != anchor.device:
-            raise TypeError("%s is on %s, theta on %s"
-                            % (name, t.device, anchor.device))
-    if tuple(anchor.shape) != (LSTM_NPARAMS,):
-        raise ValueError("theta must be [%d], got %s"
-                         % (LSTM_NPARAMS, tuple(anchor.shape)))
-    if anchor.data_ptr() % 16:
-        # the kernels read theta as 16-byte Philox blocks
-        raise ValueError("theta must be 16-byte aligned")
-
-
 def es_rollout_lstm(theta, sigma, seed, iteration, horizon, member_offset,
                     pop_shard, obs_mu, obs_nu, env_A, env_B, obs_mask=0b1111,
                     return_final=False):
@@ -1931,32 +1908,11 @@ def es_rollout_lstm(theta, sigma, seed, iteration, horizon, member_offset,
     ``pop_shard`` or ``member_offset`` (antithetic pairs), ``horizon`` or
     ``obs_mask`` out of range."""
     ops = _require_ops()
-    _check_lstm_on((("theta", theta), ("obs_mu", obs_mu), ("obs_nu", obs_nu),
-                    ("env_A", env_A), ("env_B", env_B)), theta)
-    for name, t, want in (("obs_mu", obs_mu, (OBS_DIM,)),
-                          ("obs_nu", obs_nu, (OBS_DIM,)),
-                          ("env_A", env_A, (OBS_DIM, OBS_DIM)),
-                          ("env_B", env_B, (OBS_DIM,))):
-        if tuple(t.shape) != want:
-            raise ValueError("%s must be %s, got %s"
-                             % (name, list(want), tuple(t.shape)))
-    pop_shard, member_offset = int(pop_shard), int(member_offset)
-    horizon, obs_mask = int(horizon), int(obs_mask)
-    if pop_shard < 2 or pop_shard % 2 or member_offset < 0 \
-            or member_offset % 2:
-        raise ValueError("pop_shard must be even and >= 2, member_offset "
-                         "even and >= 0 (antithetic pairs), got %d, %d"
-                         % (pop_shard, member_offset))
-    if horizon < 0:
-        raise ValueError("horizon must be >= 0, got %d" % horizon)
-    if not 0 <= obs_mask < 2 ** OBS_DIM:
-        raise ValueError("obs_mask must be in [0, %d), got %d"
-                         % (2 ** OBS_DIM, obs_mask))
+    (pop_shard, member_offset, horizon, obs_mask, fitness, obs_stat,
+     part) = _rollout_prelude(
+        theta, LSTM_NPARAMS, True, "", pop_shard, member_offset, horizon,
+        obs_mu, obs_nu, env_A, env_B, int(obs_mask))
     device = theta.device
-    fitness = torch.empty(pop_shard, dtype=torch.float32, device=device)
-    obs_stat = torch.zeros(2 * OBS_DIM + 1, dtype=torch.float32,
-                           device=device)
-    part = _partial_buffer(device, pop_shard * 2 * OBS_DIM)
     final = ()
     if return_final:
         final = tuple(
@@ -1989,7 +1945,7 @@ def lstm_policy_step(theta, x, h, c, out=None):
     named = [("theta", theta), ("x", x), ("h", h), ("c", c)]
     if out is not None:
         named += [("out[%d]" % i, t) for i, t in enumerate(out)]
-    _check_lstm_on(named, theta)
+    _check_policy_on(named, theta, LSTM_NPARAMS, True)
     if x.dim() != 2 or x.shape[1] != OBS_DIM:
         raise ValueError("x must be [batch, %d], got %s"
                          % (OBS_DIM, tuple(x.shape)))
