@@ -20,8 +20,8 @@ import collections
 import numpy as np
 
 from .gru_oracle import (  # noqa: F401  (C01, X_REL, ...: for the tests)
-    C01, EPS_SIG, EPS_TANH, N_LOGIT, SAFETY, U, X_REL, Z_REL, _sigmoid,
-    _sigmoid_slope, bf16_round, env_step, observe, tanh_slope)
+    C01, C1EM4, EPS_SIG, EPS_TANH, N_LOGIT, SAFETY, U, X_REL, Z_REL,
+    _sigmoid, _sigmoid_slope, bf16_round, env_step, observe, tanh_slope)
 
 OBS, HID, ACT, GATES = 4, 64, 2, 4  # gates i, f, g, o: torch's order
 OFF_WH, OFF_B, OFF_WO, OFF_BO, LSTM_NPARAMS = 1024, 17408, 17664, 17792, 17794
@@ -70,12 +70,22 @@ def make_policy(theta, sgn=0.0, z=None, bf16=True):
                   bf16)
 
 
-def cell(pol, x, h, c, x_slack=None):
+def cell(pol, x, h, c, x_slack=None, slip=None, with_pre=False):
     """One step for ``x`` [E][4] and the carried ``h``, ``c`` [E][64]:
-    ``(h', c', logits, tol_h, tol_c, tol_logits)``.  ``x_slack`` [E][4] is
-    what the kernel's x may differ by (the bf16 spacing where its rounding
-    is ambiguous).  With a ``bf16=False`` policy ``h`` is not rounded
-    either: the plain float64 cell."""
+    ``(h', c', logits, tol_h, tol_c, tol_logits)``; ``with_pre`` appends the
+    gate pre-activations ``(a_i, a_f, a_g, a_o)``, each [E][64].  ``x_slack``
+    [E][4] is what the kernel's x may differ by (the bf16 spacing where its
+    rounding is ambiguous).  With a ``bf16=False`` policy ``h`` is not
+    rounded either: the plain float64 cell.
+
+    ``slip`` names a deliberate mistake, for the tests that show the
+    tolerances are sharp: ``"c_rounded"`` (the carried c rounded to bf16
+    before ``f c``), ``"if_swapped"`` (``c' = i c + f g``), ``"tanh_c_old"``
+    (``h' = o tanh(c)`` of the incoming c), ``"h_rounded"`` (the logits read
+    ``bf16(h')``).  The tolerances returned with a slip are those of the
+    slipped values and serve no comparison."""
+    assert slip in (None, "c_rounded", "if_swapped", "tanh_c_old",
+                    "h_rounded"), slip
     x = np.asarray(x, dtype=np.float64)
     h = np.asarray(h, dtype=np.float64)
     c = np.asarray(c, dtype=np.float64)
@@ -102,6 +112,10 @@ def cell(pol, x, h, c, x_slack=None):
     err_g = EPS_TANH + tanh_slope(a_g, e_g) * e_g
     # the kernel: p = i * g (rounded), c' = fmaf(f, c, p) (rounded); c is the
     # caller's fp32 value, exact on both sides
+    if slip == "c_rounded":
+        c = bf16_round(c)[0]
+    elif slip == "if_swapped":
+        ig, fg = fg, ig
     p = ig * gg
     err_p = err_i * (np.abs(gg) + err_g) + ig * err_g
     err_p = err_p + U * (np.abs(p) + err_p)
@@ -109,15 +123,71 @@ def cell(pol, x, h, c, x_slack=None):
     tol_c = err_f * np.abs(c) + err_p
     tol_c = tol_c + U * (np.abs(cn) + tol_c)
     # h' = o * tanh(c') (rounded), tanh of the kernel's own c'
-    tc = np.tanh(cn)
+    tc = np.tanh(c if slip == "tanh_c_old" else cn)
     err_t = EPS_TANH + tanh_slope(cn, tol_c) * tol_c
     hn = og * tc
     tol_h = err_o * (np.abs(tc) + err_t) + og * err_t
     tol_h = tol_h + U * (np.abs(hn) + tol_h)
     # logits from the kernel's own fp32 h', which is within tol_h of hn
-    t = hn[:, None, :] * pol.wo[None, :, :]               # [E][2][64]
+    hl = bf16_round(hn)[0] if slip == "h_rounded" else hn
+    t = hl[:, None, :] * pol.wo[None, :, :]               # [E][2][64]
     logits = t.sum(-1) + pol.bo
     tol_l = (tol_h @ np.abs(pol.wo).T + np.abs(hn) @ pol.wo_slack.T
              + N_LOGIT * U * (np.abs(t).sum(-1) + np.abs(pol.bo))
              + pol.bo_err)
+    if with_pre:
+        return hn, cn, logits, tol_h, tol_c, tol_l, (a_i, a_f, a_g, a_o)
     return hn, cn, logits, tol_h, tol_c, tol_l
+
+
+Rollout = collections.namedtuple("Rollout", [
+    "s",        # [steps + 1][E][4]   env state, s[0] = s0
+    "h",        # [steps + 1][E][64]  carried hidden state, h[0] = 0
+    "c",        # [steps + 1][E][64]  carried cell state, c[0] = 0
+    "x",        # [steps][E][4]       what the policy saw at step t
+    "x_raw",    # [steps][E][4]       normalised obs before mask and clamp
+    "pre",      # [steps][4][E][64]   gate pre-activations a_i, a_f, a_g, a_o
+    "logits",   # [steps][E][2]
+    "tol_l",    # [steps][E][2]       cell's logits tolerance at step t
+    "action"])  # [steps][E]          l1 > l0
+
+
+def rollout(pol, obs_mu, obs_nu, obs_mask, env_A, env_B, s0, steps):
+    """``observe -> cell -> env_step`` chained for ``steps`` steps from the
+    state ``s0`` [E][4] and zero hidden and cell states.  The state, the
+    hidden and the cell state are rounded to fp32 between steps, as the
+    kernel holds them.
+
+    This serves only to choose test inputs and to state conditions about
+    them on the CPU (how many steps are decided, where the clamp fires, how
+    far the gates saturate, how large c grows).  Its tolerances are those of
+    one step: nothing here bounds the kernel over several steps, and no
+    comparison with the kernel goes through it."""
+    mu = np.asarray(obs_mu, dtype=np.float32).astype(np.float64)
+    nu = np.asarray(obs_nu, dtype=np.float32).astype(np.float64)
+    s = np.asarray(s0, dtype=np.float32)
+    h = np.zeros((s.shape[0], HID), dtype=np.float32)
+    c = np.zeros((s.shape[0], HID), dtype=np.float32)
+    out = {k: [] for k in Rollout._fields}
+    out["s"].append(s)
+    out["h"].append(h)
+    out["c"].append(c)
+    for _t in range(steps):
+        x, x_slack = observe(s, mu, nu, obs_mask)
+        hn, cn, logits, _tol_h, _tol_c, tol_l, pre = cell(
+            pol, x, h, c, x_slack, with_pre=True)
+        action = logits[:, 1] > logits[:, 0]
+        s = env_step(s, action, env_A, env_B)[0].astype(np.float32)
+        h, c = hn.astype(np.float32), cn.astype(np.float32)
+        out["x"].append(x)
+        out["x_raw"].append(
+            (out["s"][-1].astype(np.float64) - mu) / np.sqrt(nu + C1EM4))
+        out["pre"].append(np.stack(pre))
+        out["logits"].append(logits)
+        out["tol_l"].append(tol_l)
+        out["action"].append(action)
+        out["s"].append(s)
+        out["h"].append(h)
+        out["c"].append(c)
+    return Rollout(*(np.stack(out[k]) if out[k] else np.zeros((0,))
+                     for k in Rollout._fields))

@@ -142,8 +142,9 @@ def least_share(name, seed=None, members=MEMBERS, horizons=None):
 # ---- the comparison ---------------------------------------------------------
 
 def worse(a, b):
-    """max(a, b) that a NaN wins: a kernel that returns NaN must fail."""
-    return a if b <= a else b
+    """max(a, b) that a NaN wins from either side: a kernel that returns
+    NaN must fail, whichever member it is in."""
+    return b if b > a or b != b else a
 
 
 def compare_member(c, member, mask, h, s0, hid0, s1, hid1, f0, f1):

@@ -238,6 +238,12 @@ def test_nan_fails():
         bad[field].reshape(-1)[-1] = np.nan
         assert not S.passes(S.compare_pair(S.case("base"), S.OFFSET, 0b1111,
                                            8, runs[8], tuple(bad))), field
+    # a NaN in the first member is not covered up by the members after it
+    bad = [a.copy() for a in runs[9]]
+    bad[3][0, 0, 0] = np.nan
+    v = S.compare_pair(S.case("base"), S.OFFSET, 0b1111, 8, runs[8],
+                       tuple(bad))
+    assert v.worst["h"] != v.worst["h"] and not S.passes(v)
     wrong_count = [a.copy() for a in runs[9]]
     wrong_count[1][8] += 1
     assert not S.passes(S.compare_pair(S.case("base"), S.OFFSET, 0b1111, 8,
