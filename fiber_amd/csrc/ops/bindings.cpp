@@ -122,6 +122,13 @@ extern "C" __global__ void es_rollout_lstm(
 extern "C" __global__ void lstm_policy_step(const float*, const float*,
                                             const float*, const float*, int,
                                             float*, float*, float*);
+// CartPole environment (cartpole_kernels.hip)
+extern "C" __global__ void es_rollout_mlp_cartpole(
+    const float*, float, uint32_t, uint32_t, int, int, const float*,
+    const float*, const float*, float*, float*, int*, float*);
+extern "C" __global__ void cartpole_stat_reduce(const float*, int, float*);
+extern "C" __global__ void cartpole_step(const float*, const int*,
+                                         const float*, int, float*, int*);
 // wide MLP policies (wide_kernels.hip)
 #define WIDE_DECL(H)                                                         \
   extern "C" __global__ void es_rollout_mlp_wide_##H(                        \
@@ -471,6 +478,48 @@ static void launch_lstm_policy_step(uintptr_t theta, uintptr_t x, uintptr_t h,
                      (const float*)x, (const float*)h, (const float*)c, batch,
                      (float*)logits, (float*)hnew, (float*)cnew);
   check(hipGetLastError(), "lstm_policy_step launch");
+}
+
+// The MLP rollout on CartPole.  stat_part is [pop_shard][9]: the count of
+// steps taken is data and rides with the eight sums.  lengths / final_state
+// may be 0.
+static void launch_rollout_cartpole(uintptr_t theta, double sigma,
+                                    uint32_t seed, uint32_t iter, int horizon,
+                                    int member_offset, int pop_shard,
+                                    uintptr_t obs_mu, uintptr_t obs_nu,
+                                    uintptr_t cart, uintptr_t fitness,
+                                    uintptr_t stat_part, uintptr_t obs_stat,
+                                    uintptr_t lengths, uintptr_t final_state,
+                                    uintptr_t stream) {
+  if (pop_shard < 1)
+    throw std::runtime_error(
+        "es_rollout_mlp_cartpole: pop_shard must be >= 1");
+  // 64 * horizon, a member's step count, stays exact in fp32
+  if (horizon < 0 || horizon >= (1 << 18))
+    throw std::runtime_error(
+        "es_rollout_mlp_cartpole: horizon must be in [0, 2^18)");
+  hipLaunchKernelGGL(es_rollout_mlp_cartpole, dim3(pop_shard), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)theta, (float)sigma,
+                     seed, iter, horizon, member_offset,
+                     (const float*)obs_mu, (const float*)obs_nu,
+                     (const float*)cart, (float*)fitness, (float*)stat_part,
+                     (int*)lengths, (float*)final_state);
+  check(hipGetLastError(), "es_rollout_mlp_cartpole launch");
+  hipLaunchKernelGGL(cartpole_stat_reduce, dim3(2 * OBS_HOST + 1), dim3(256),
+                     0, (hipStream_t)stream, (const float*)stat_part,
+                     pop_shard, (float*)obs_stat);
+  check(hipGetLastError(), "cartpole_stat_reduce launch");
+}
+
+static void launch_cartpole_step(uintptr_t state, uintptr_t action,
+                                 uintptr_t cart, int n, uintptr_t next_state,
+                                 uintptr_t done, uintptr_t stream) {
+  if (n < 1) throw std::runtime_error("cartpole_step: n must be >= 1");
+  hipLaunchKernelGGL(cartpole_step, dim3((unsigned)((n + 255) / 256)),
+                     dim3(256), 0, (hipStream_t)stream, (const float*)state,
+                     (const int*)action, (const float*)cart, n,
+                     (float*)next_state, (int*)done);
+  check(hipGetLastError(), "cartpole_step launch");
 }
 
 // launch_rollout for a wide MLP policy (hidden 128 or 256).  final_state
@@ -1188,6 +1237,15 @@ PYBIND11_MODULE(_ops, m) {
         py::arg("x"), py::arg("h"), py::arg("c"), py::arg("batch"),
         py::arg("logits"), py::arg("hnew"), py::arg("cnew"),
         py::arg("stream"));
+  m.def("es_rollout_mlp_cartpole", &launch_rollout_cartpole,
+        py::arg("theta"), py::arg("sigma"), py::arg("seed"), py::arg("iter"),
+        py::arg("horizon"), py::arg("member_offset"), py::arg("pop_shard"),
+        py::arg("obs_mu"), py::arg("obs_nu"), py::arg("cart"),
+        py::arg("fitness"), py::arg("stat_part"), py::arg("obs_stat"),
+        py::arg("lengths"), py::arg("final_state"), py::arg("stream"));
+  m.def("cartpole_step", &launch_cartpole_step, py::arg("state"),
+        py::arg("action"), py::arg("cart"), py::arg("n"),
+        py::arg("next_state"), py::arg("done"), py::arg("stream"));
   m.def("es_rollout_mlp_wide", &launch_rollout_wide, py::arg("theta"),
         py::arg("hidden"), py::arg("sigma"), py::arg("seed"),
         py::arg("iter"), py::arg("horizon"), py::arg("member_offset"),

@@ -5,6 +5,7 @@ from .engine import (  # noqa: F401
     init_theta,
     make_env_params,
 )
+from .cartpole import CartPoleESEngine  # noqa: F401
 from .ga import GAConfig, GAEngine  # noqa: F401
 from .lstm import LSTMESEngine, init_theta_lstm  # noqa: F401
 from .map_elites import MapElitesConfig, MapElitesEngine  # noqa: F401

@@ -165,8 +165,14 @@ class RolloutESEngine(ObsNormaliser):
         self.adam_v = torch.zeros_like(self.theta)
         self.t_step = 0
 
-        self.env_A, self.env_B = resolve_env(config, device, env_params)
+        self._resolve_env(env_params)
         self._init_normaliser()
+
+    def _resolve_env(self, env_params):
+        """Keep the environment ``_rollout`` runs on; the synthetic linear
+        one unless the engine has another."""
+        self.env_A, self.env_B = resolve_env(self.cfg, self.device,
+                                             env_params)
 
     def _init_theta(self):
         """The initial flat theta ``[nparams]`` on ``self.device``."""

@@ -5,6 +5,8 @@ an error — there is deliberately NO eager/PyTorch fallback for the hot
 ops, so a silently-degraded bench is impossible.
 """
 
+import math
+
 import torch
 
 _OPS = None
@@ -1974,6 +1976,147 @@ def lstm_policy_step(theta, x, h, c, out=None):
                              c.data_ptr(), batch, out[0].data_ptr(),
                              out[1].data_ptr(), out[2].data_ptr(), _stream())
     return out[0], out[1], out[2]
+
+
+# ---------------------------------------------------------------------------
+# CartPole environment for the MLP policy (cartpole_kernels.hip)
+# ---------------------------------------------------------------------------
+
+CART_NPARAMS = 8
+CART_THETA_MAX = 0.5     # the kernels' sin / cos polynomials hold up to here
+CART_HORIZON_MAX = 2 ** 18   # 64 * horizon stays exact in fp32
+
+
+def cartpole_params(gravity=9.8, masscart=1.0, masspole=0.1, length=0.5,
+                    force_mag=10.0, tau=0.02, x_threshold=2.4,
+                    theta_threshold=12 * 2 * math.pi / 360, device=None):
+    """``cart[8]`` (fp32 on ``device``) for the CartPole kernels, Gym
+    CartPole-v1's values by default: gravity, masscart, masspole, length
+    (half the pole's), force_mag, tau, x_threshold, theta_threshold (rad).
+    ValueError for an entry that is not positive and finite, or a
+    ``theta_threshold`` above ``CART_THETA_MAX``."""
+    vals = [float(v) for v in (gravity, masscart, masspole, length,
+                               force_mag, tau, x_threshold, theta_threshold)]
+    if not all(math.isfinite(v) and v > 0.0 for v in vals):
+        raise ValueError("every CartPole parameter must be positive and "
+                         "finite, got %s" % (vals,))
+    if vals[7] > CART_THETA_MAX:
+        raise ValueError("theta_threshold must be <= %g rad, got %g"
+                         % (CART_THETA_MAX, vals[7]))
+    return torch.tensor(vals, dtype=torch.float32, device=device)
+
+
+def es_rollout_mlp_cartpole(theta, sigma, seed, iteration, horizon,
+                            member_offset, pop_shard, obs_mu, obs_nu, cart,
+                            return_lengths=False, return_final=False):
+    """``es_rollout_mlp`` on CartPole (``cart`` from ``cartpole_params``):
+    one launch rolls out ``pop_shard`` perturbed members x 64 environments
+    until each has failed or taken ``horizon`` steps.  The noise is the
+    ``es_rollout_mlp`` stream, so ``es_grad`` regenerates it.  The reward is
+    1 per step taken: ``fitness[m]`` is the mean episode length of member
+    ``m``.  Finished environments cost no matmul work: the live ones are
+    packed into the leading MFMA column tiles, and a member whose
+    environments have all ended leaves the loop.
+
+    Returns ``(fitness[pop_shard], obs_stat[9])``; ``obs_stat`` covers the
+    states that were presented to the policy, and ``obs_stat[8]`` is their
+    count, the steps taken.  ``return_lengths`` adds int32
+    ``lengths[pop_shard][64]``, ``return_final`` then
+    ``final_state[pop_shard][64][4]`` (a finished environment's state is the
+    one it failed in).  Asking for them does not change a bit of the other
+    two.  ``horizon`` may be 0.
+
+    TypeError for dtype, device or contiguity, ValueError for shapes, an odd
+    ``pop_shard`` or ``member_offset`` (antithetic pairs) or ``horizon``
+    outside ``[0, CART_HORIZON_MAX)``."""
+    ops = _require_ops()
+    _check_policy_on((("theta", theta), ("obs_mu", obs_mu),
+                      ("obs_nu", obs_nu), ("cart", cart)), theta, NPARAMS,
+                     False)
+    for name, t, want in (("obs_mu", obs_mu, (OBS_DIM,)),
+                          ("obs_nu", obs_nu, (OBS_DIM,)),
+                          ("cart", cart, (CART_NPARAMS,))):
+        if tuple(t.shape) != want:
+            raise ValueError("%s must be %s, got %s"
+                             % (name, list(want), tuple(t.shape)))
+    pop_shard, member_offset = int(pop_shard), int(member_offset)
+    horizon = int(horizon)
+    if pop_shard < 2 or pop_shard % 2 or member_offset < 0 \
+            or member_offset % 2:
+        raise ValueError("pop_shard must be even and >= 2, member_offset "
+                         "even and >= 0 (antithetic pairs), got %d, %d"
+                         % (pop_shard, member_offset))
+    if not 0 <= horizon < CART_HORIZON_MAX:
+        raise ValueError("horizon must be in [0, %d), got %d"
+                         % (CART_HORIZON_MAX, horizon))
+    device = theta.device
+    fitness = torch.empty(pop_shard, dtype=torch.float32, device=device)
+    obs_stat = torch.empty(2 * OBS_DIM + 1, dtype=torch.float32,
+                           device=device)
+    part = _partial_buffer(device, pop_shard * (2 * OBS_DIM + 1))
+    extra = []
+    if return_lengths:
+        extra.append(torch.empty(pop_shard, ENVS_PER_MEMBER,
+                                 dtype=torch.int32, device=device))
+    if return_final:
+        extra.append(torch.empty(pop_shard, ENVS_PER_MEMBER, OBS_DIM,
+                                 dtype=torch.float32, device=device))
+    with torch.cuda.device(device):
+        ops.es_rollout_mlp_cartpole(
+            theta.data_ptr(), float(sigma), int(seed) & 0xFFFFFFFF,
+            int(iteration) & 0xFFFFFFFF, horizon, member_offset, pop_shard,
+            obs_mu.data_ptr(), obs_nu.data_ptr(), cart.data_ptr(),
+            fitness.data_ptr(), part.data_ptr(), obs_stat.data_ptr(),
+            extra[0].data_ptr() if return_lengths else 0,
+            extra[-1].data_ptr() if return_final else 0, _stream())
+    return (fitness, obs_stat) + tuple(extra)
+
+
+def cartpole_step(state, action, cart, out=None):
+    """One CartPole step outside a rollout, with the rollout's physics:
+    ``(next_state[n][4], done[n])`` for fp32 ``state[n][4]`` (x, x_dot,
+    theta, theta_dot) and int32 ``action[n]`` (0 pushes left, anything else
+    right), ``n >= 1``, all on ``cart``'s device.  ``done`` is int32, 1 where
+    the new state is past a threshold.  ``out``, if given, is a pair of
+    contiguous tensors ``(next_state, done)`` that are written and returned;
+    ``next_state`` may be ``state`` itself.  The kernel moves states as
+    16-byte vectors: ``state`` and ``next_state`` must start on a 16-byte
+    boundary.  Everything is validated before the launch."""
+    ops = _require_ops()
+    _check(cart, "cart")
+    if tuple(cart.shape) != (CART_NPARAMS,):
+        raise ValueError("cart must be [%d], got %s"
+                         % (CART_NPARAMS, tuple(cart.shape)))
+    if state.dim() != 2 or state.shape[1] != OBS_DIM:
+        raise ValueError("state must be [n, %d], got %s"
+                         % (OBS_DIM, tuple(state.shape)))
+    n = state.shape[0]
+    if n < 1 or n * OBS_DIM >= 2 ** 31:
+        raise ValueError("n must be in [1, 2^31 / %d), got %d"
+                         % (OBS_DIM, n))
+    if out is None:
+        out = (torch.empty_like(state),
+               torch.empty(n, dtype=torch.int32, device=state.device))
+    named = (("state", state, torch.float32, (n, OBS_DIM)),
+             ("action", action, torch.int32, (n,)),
+             ("out[0]", out[0], torch.float32, (n, OBS_DIM)),
+             ("out[1]", out[1], torch.int32, (n,)))
+    for name, t, dtype, want in named:
+        _check(t, name, dtype)
+        if t.device != cart.device:
+            raise TypeError("%s is on %s, cart on %s"
+                            % (name, t.device, cart.device))
+        if tuple(t.shape) != want:
+            raise ValueError("%s must be %s, got %s"
+                             % (name, list(want), tuple(t.shape)))
+    for name, t in (("state", state), ("out[0]", out[0])):
+        if t.data_ptr() % 16:
+            raise ValueError("%s must be 16-byte aligned" % name)
+    with torch.cuda.device(cart.device):
+        ops.cartpole_step(state.data_ptr(), action.data_ptr(),
+                          cart.data_ptr(), n, out[0].data_ptr(),
+                          out[1].data_ptr(), _stream())
+    return out[0], out[1]
 
 
 def ops_available():

@@ -75,6 +75,11 @@ class build_ext(_build_ext):
             # (profiles/lstm.md)
             os.path.join(ROOT, "fiber_amd", "csrc", "ops",
                          "lstm_kernels.hip"),
+            # CartPole environment for the MLP policy: the same arrangement,
+            # on this command 72 VGPRs or fewer and no scratch
+            # (profiles/cartpole.md)
+            os.path.join(ROOT, "fiber_amd", "csrc", "ops",
+                         "cartpole_kernels.hip"),
             os.path.join(ROOT, "fiber_amd", "csrc", "ops", "bindings.cpp"),
         ]
         # GRU recurrent policy: shares es_kernels.hip's device code like the
