@@ -129,6 +129,11 @@ extern "C" __global__ void es_rollout_mlp_cartpole(
 extern "C" __global__ void cartpole_stat_reduce(const float*, int, float*);
 extern "C" __global__ void cartpole_step(const float*, const int*,
                                          const float*, int, float*, int*);
+// LSTM policy on CartPole (lstm_cartpole_kernels.hip)
+extern "C" __global__ void es_rollout_lstm_cartpole(
+    const float*, float, uint32_t, uint32_t, int, int, const float*,
+    const float*, const float*, int, float*, float*, int*, float*, float*,
+    float*);
 // wide MLP policies (wide_kernels.hip)
 #define WIDE_DECL(H)                                                         \
   extern "C" __global__ void es_rollout_mlp_wide_##H(                        \
@@ -520,6 +525,38 @@ static void launch_cartpole_step(uintptr_t state, uintptr_t action,
                      (const int*)action, (const float*)cart, n,
                      (float*)next_state, (int*)done);
   check(hipGetLastError(), "cartpole_step launch");
+}
+
+// The LSTM rollout on CartPole: 512 threads per member, stat_part as above.
+// lengths / final_state / final_hidden / final_cell may be 0.
+static void launch_rollout_lstm_cartpole(
+    uintptr_t theta, double sigma, uint32_t seed, uint32_t iter, int horizon,
+    int member_offset, int pop_shard, uintptr_t obs_mu, uintptr_t obs_nu,
+    uintptr_t cart, int obs_mask, uintptr_t fitness, uintptr_t stat_part,
+    uintptr_t obs_stat, uintptr_t lengths, uintptr_t final_state,
+    uintptr_t final_hidden, uintptr_t final_cell, uintptr_t stream) {
+  if (pop_shard < 1)
+    throw std::runtime_error(
+        "es_rollout_lstm_cartpole: pop_shard must be >= 1");
+  // 64 * horizon, a member's step count, stays exact in fp32
+  if (horizon < 0 || horizon >= (1 << 18))
+    throw std::runtime_error(
+        "es_rollout_lstm_cartpole: horizon must be in [0, 2^18)");
+  if (obs_mask < 0 || obs_mask >= (1 << OBS_HOST))
+    throw std::runtime_error(
+        "es_rollout_lstm_cartpole: obs_mask must be in [0, 16)");
+  hipLaunchKernelGGL(es_rollout_lstm_cartpole, dim3(pop_shard), dim3(512), 0,
+                     (hipStream_t)stream, (const float*)theta, (float)sigma,
+                     seed, iter, horizon, member_offset,
+                     (const float*)obs_mu, (const float*)obs_nu,
+                     (const float*)cart, obs_mask, (float*)fitness,
+                     (float*)stat_part, (int*)lengths, (float*)final_state,
+                     (float*)final_hidden, (float*)final_cell);
+  check(hipGetLastError(), "es_rollout_lstm_cartpole launch");
+  hipLaunchKernelGGL(cartpole_stat_reduce, dim3(2 * OBS_HOST + 1), dim3(256),
+                     0, (hipStream_t)stream, (const float*)stat_part,
+                     pop_shard, (float*)obs_stat);
+  check(hipGetLastError(), "cartpole_stat_reduce launch");
 }
 
 // launch_rollout for a wide MLP policy (hidden 128 or 256).  final_state
@@ -1246,6 +1283,13 @@ PYBIND11_MODULE(_ops, m) {
   m.def("cartpole_step", &launch_cartpole_step, py::arg("state"),
         py::arg("action"), py::arg("cart"), py::arg("n"),
         py::arg("next_state"), py::arg("done"), py::arg("stream"));
+  m.def("es_rollout_lstm_cartpole", &launch_rollout_lstm_cartpole,
+        py::arg("theta"), py::arg("sigma"), py::arg("seed"), py::arg("iter"),
+        py::arg("horizon"), py::arg("member_offset"), py::arg("pop_shard"),
+        py::arg("obs_mu"), py::arg("obs_nu"), py::arg("cart"),
+        py::arg("obs_mask"), py::arg("fitness"), py::arg("stat_part"),
+        py::arg("obs_stat"), py::arg("lengths"), py::arg("final_state"),
+        py::arg("final_hidden"), py::arg("final_cell"), py::arg("stream"));
   m.def("es_rollout_mlp_wide", &launch_rollout_wide, py::arg("theta"),
         py::arg("hidden"), py::arg("sigma"), py::arg("seed"),
         py::arg("iter"), py::arg("horizon"), py::arg("member_offset"),

@@ -89,7 +89,9 @@ struct LstmLds {
   alignas(16) float small[LS_BO + ACT + 2];
   alignas(16) __hip_bfloat16 xb[ENVS][S1];
   alignas(16) __hip_bfloat16 zero16[8];  // narrow kgrp>0 fragments
-  float S[2][ENVS][OBS];     // env state (double-buffered)
+  // env state (double-buffered); es_rollout_lstm_cartpole reads a row as one
+  // 16-byte vector
+  alignas(16) float S[2][ENVS][OBS];
   float lpart[4][ENVS][2];   // per-strip logits partials
   float ostat[2 * OBS + 1];
   // fp32 h' of the last step, for final_hidden / Hnew: kept here, not in
@@ -240,17 +242,28 @@ __device__ __forceinline__ void lstm_load(const float* __restrict__ theta,
 // hfin[env][row] unless hfin is null (wave-uniform), and the logits partials
 // of its 32 envs to lrow = lpart[strip].  No barrier inside; the caller
 // separates hcur / hnext / lpart users.
+//
+// SKIP (es_rollout_lstm_cartpole): bit cc of the wave-uniform `tiles` says
+// that column tile cc of this half still has a live environment.  A dead
+// tile costs no MFMA, no transcendental and no store; c[cc] keeps its value
+// and the pair-wide logits reduce gets zeros for it.
+template <bool SKIP = false>
 __device__ __forceinline__ void lstm_cell(
     const LstmRegs& R, const __hip_bfloat16 (*wi)[HID][S1],
     const __hip_bfloat16* __restrict__ xb, const __hip_bfloat16* zero16,
     const __hip_bfloat16* __restrict__ hcur,
     __hip_bfloat16* __restrict__ hnext, f32x4 (&c)[2],
     float* __restrict__ hfin, float (*lrow)[2], int strip, int half,
-    int lane) {
+    int lane, int tiles = 3) {
   const int drow = strip * 16 + (lane >> 4) * 4;
   float p0[2], p1[2];
 #pragma unroll
   for (int cc = 0; cc < 2; ++cc) {
+    if (SKIP && !((tiles >> cc) & 1)) {
+      p0[cc] = 0.f;
+      p1[cc] = 0.f;
+      continue;
+    }
     const int bcol = (half * 2 + cc) * 16 + (lane & 15);
     // three B-side reads feed twelve MFMAs
     const bf16x8 bx = *strip_frag_ptr<S1, true>(xb, zero16, bcol, 0, lane >> 4);
@@ -305,6 +318,11 @@ __device__ __forceinline__ void lstm_cell(
   }
   logits_reduce_swap(p0[0], p1[0], p0[1], p1[1], lrow, half * 2, lane);
 }
+
+// lstm_cartpole_kernels.hip includes this file with
+// LSTM_KERNELS_SHARED_ONLY defined, for everything above without the
+// kernels below (the arrangement of es_kernels.hip).
+#ifndef LSTM_KERNELS_SHARED_ONLY
 
 extern "C" __global__ void __launch_bounds__(LSTM_THREADS, LSTM_WAVES)
 es_rollout_lstm(const float* __restrict__ theta, float sigma, uint32_t seed,
@@ -537,3 +555,4 @@ lstm_policy_step(const float* __restrict__ theta, const float* __restrict__ X,
                               L.lpart[3][e][a];
   }
 }
+#endif  // LSTM_KERNELS_SHARED_ONLY

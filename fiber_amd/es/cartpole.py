@@ -11,8 +11,9 @@ The environment is ``cart[8]`` (``ops.cartpole_params``).  Every iteration
 starts its 64 episodes per member from ``0.05 * z``, ``z`` drawn per (seed,
 iteration): common random numbers across the members.
 
-Limits: one GPU; there is no POET / ``ESPopulation``, novelty, GA or
-recurrent variant on this environment.
+Limits: one GPU; there is no POET / ``ESPopulation``, novelty or GA variant
+on this environment.  The recurrent variant is ``LSTMCartPoleESEngine``
+(lstm_cartpole.py), which can also hide the velocities from the policy.
 """
 
 import dataclasses

@@ -2119,5 +2119,95 @@ def cartpole_step(state, action, cart, out=None):
     return out[0], out[1]
 
 
+# ---------------------------------------------------------------------------
+# LSTM policy on CartPole (lstm_cartpole_kernels.hip)
+# ---------------------------------------------------------------------------
+
+def es_rollout_lstm_cartpole(theta, sigma, seed, iteration, horizon,
+                             member_offset, pop_shard, obs_mu, obs_nu, cart,
+                             obs_mask=0b1111, return_lengths=False,
+                             return_final=False):
+    """``es_rollout_lstm``'s policy (``theta[LSTM_NPARAMS]``, hidden and cell
+    state starting at zero) on ``es_rollout_mlp_cartpole``'s environment
+    (``cart`` from ``cartpole_params``): one launch rolls out ``pop_shard``
+    perturbed members x 64 environments until each has failed or taken
+    ``horizon`` steps.  The noise is the ``es_rollout_lstm`` stream, so
+    ``es_grad(nparams=LSTM_NPARAMS)`` regenerates it.  Bit ``d`` of
+    ``obs_mask`` says that state dim ``d`` (x, x_dot, theta, theta_dot) is
+    visible; a hidden dim reaches the policy as 0 and the statistics still
+    count it.  ``0b0101`` hides both velocities.  An environment keeps its
+    MFMA column for the whole episode; a column tile whose 16 environments
+    have all ended costs no matmul work, and a member whose environments
+    have all ended leaves the loop.
+
+    Returns ``(fitness[pop_shard], obs_stat[9])`` as
+    ``es_rollout_mlp_cartpole`` does: mean episode length, and the sums over
+    the states presented to the policy with their count, the steps taken, in
+    ``obs_stat[8]``.  ``return_lengths`` adds int32 ``lengths[pop_shard][64]``;
+    ``return_final`` then ``final_state[pop_shard][64][4]`` (a finished
+    environment's state is the one it failed in),
+    ``final_hidden[pop_shard][64][64]`` and ``final_cell[pop_shard][64][64]``:
+    for an environment still alive the fp32 ``h'`` the last logits were read
+    from and the carried cell state, for one that has ended zeros.  Asking
+    for them does not change a bit of the others.  ``horizon`` may be 0.
+
+    Everything is validated before the launch; ``cart`` goes through
+    ``cartpole_params``' checks, which reads its eight values back to the
+    host.  TypeError for dtype, device or contiguity, ValueError for shapes,
+    alignment, an odd ``pop_shard`` or ``member_offset`` (antithetic pairs),
+    ``horizon`` outside ``[0, CART_HORIZON_MAX)``, ``obs_mask`` outside
+    ``[0, 16)`` or a ``cart`` that ``cartpole_params`` refuses."""
+    ops = _require_ops()
+    _check_policy_on((("theta", theta), ("obs_mu", obs_mu),
+                      ("obs_nu", obs_nu), ("cart", cart)), theta,
+                     LSTM_NPARAMS, True)
+    for name, t, want in (("obs_mu", obs_mu, (OBS_DIM,)),
+                          ("obs_nu", obs_nu, (OBS_DIM,)),
+                          ("cart", cart, (CART_NPARAMS,))):
+        if tuple(t.shape) != want:
+            raise ValueError("%s must be %s, got %s"
+                             % (name, list(want), tuple(t.shape)))
+    pop_shard, member_offset = int(pop_shard), int(member_offset)
+    horizon, obs_mask = int(horizon), int(obs_mask)
+    if pop_shard < 2 or pop_shard % 2 or member_offset < 0 \
+            or member_offset % 2:
+        raise ValueError("pop_shard must be even and >= 2, member_offset "
+                         "even and >= 0 (antithetic pairs), got %d, %d"
+                         % (pop_shard, member_offset))
+    if not 0 <= horizon < CART_HORIZON_MAX:
+        raise ValueError("horizon must be in [0, %d), got %d"
+                         % (CART_HORIZON_MAX, horizon))
+    if not 0 <= obs_mask < 2 ** OBS_DIM:
+        raise ValueError("obs_mask must be in [0, %d), got %d"
+                         % (2 ** OBS_DIM, obs_mask))
+    cartpole_params(*cart.tolist())
+    device = theta.device
+    fitness = torch.empty(pop_shard, dtype=torch.float32, device=device)
+    obs_stat = torch.empty(2 * OBS_DIM + 1, dtype=torch.float32,
+                           device=device)
+    part = _partial_buffer(device, pop_shard * (2 * OBS_DIM + 1))
+    lengths = None
+    if return_lengths:
+        lengths = torch.empty(pop_shard, ENVS_PER_MEMBER, dtype=torch.int32,
+                              device=device)
+    final = ()
+    if return_final:
+        final = tuple(
+            torch.empty(pop_shard, ENVS_PER_MEMBER, n, dtype=torch.float32,
+                        device=device) for n in (OBS_DIM, HIDDEN, HIDDEN))
+    with torch.cuda.device(device):
+        ops.es_rollout_lstm_cartpole(
+            theta.data_ptr(), float(sigma), int(seed) & 0xFFFFFFFF,
+            int(iteration) & 0xFFFFFFFF, horizon, member_offset, pop_shard,
+            obs_mu.data_ptr(), obs_nu.data_ptr(), cart.data_ptr(), obs_mask,
+            fitness.data_ptr(), part.data_ptr(), obs_stat.data_ptr(),
+            lengths.data_ptr() if return_lengths else 0,
+            *([t.data_ptr() for t in final] or [0, 0, 0]), _stream())
+    out = (fitness, obs_stat)
+    if return_lengths:
+        out += (lengths,)
+    return out + final
+
+
 def ops_available():
     return _OPS is not None

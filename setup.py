@@ -80,6 +80,12 @@ class build_ext(_build_ext):
             # (profiles/cartpole.md)
             os.path.join(ROOT, "fiber_amd", "csrc", "ops",
                          "cartpole_kernels.hip"),
+            # LSTM policy on CartPole: includes the shared device code of
+            # lstm_kernels.hip (LSTM_KERNELS_SHARED_ONLY) and cart_physics.h,
+            # a translation unit of its own like the two above; on this
+            # command 122 VGPRs and no scratch (profiles/lstm_cartpole.md)
+            os.path.join(ROOT, "fiber_amd", "csrc", "ops",
+                         "lstm_cartpole_kernels.hip"),
             os.path.join(ROOT, "fiber_amd", "csrc", "ops", "bindings.cpp"),
         ]
         # GRU recurrent policy: shares es_kernels.hip's device code like the
@@ -103,6 +109,7 @@ class build_ext(_build_ext):
             os.path.join(ROOT, "fiber_amd", "csrc", "ops", "ga_shared.h"),
             os.path.join(ROOT, "fiber_amd", "csrc", "ops", "bc_epilogue.h"),
             os.path.join(ROOT, "fiber_amd", "csrc", "ops", "me_grid.h"),
+            os.path.join(ROOT, "fiber_amd", "csrc", "ops", "cart_physics.h"),
         ]
         if os.path.exists(out):
             newest_src = max(os.path.getmtime(s)
