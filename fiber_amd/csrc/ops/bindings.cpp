@@ -71,6 +71,15 @@ extern "C" __global__ void es_rollout_mlp_sigma(
 extern "C" __global__ void es_grad_sigma(const float*, const float*, int,
                                          int, int, uint32_t, uint32_t, int,
                                          float*);
+// low-rank correlated perturbation kernels (lowrank_kernels.hip)
+extern "C" __global__ void es_rollout_mlp_lowrank(
+    const float*, float, const float*, const float*, float, int, uint32_t,
+    uint32_t, int, int, const float*, const float*, const float*,
+    const float*, float*, float*, float*);
+extern "C" __global__ void es_perturb_lowrank(const float*, float,
+                                              const float*, const float*,
+                                              float, int, uint32_t, uint32_t,
+                                              int, float*);
 // Deep GA kernels (ga_kernels.hip)
 extern "C" __global__ void ga_parents(uint32_t, uint32_t, int, int, uint32_t,
                                       int*, int*);
@@ -753,6 +762,66 @@ static void launch_grad_sigma(uintptr_t wdiff, uintptr_t wsum,
   }
 }
 
+// ---- low-rank perturbation launchers ----------------------------------------
+// Both kernels sample from scale * I + dirs^t mix dirs with dirs [J][NPARAMS]
+// and mix [J][J]; the kernels' scratch holds LOWRANK_DIRS_MAX directions.
+#define LOWRANK_DIRS_MAX_HOST 32
+
+static void check_lowrank(const char* op, int J, int member_offset,
+                          int members) {
+  if (J < 0 || J > LOWRANK_DIRS_MAX_HOST)
+    throw std::runtime_error(std::string(op) + ": J out of range");
+  if (member_offset < 0 || (member_offset & 1) ||
+      members > 0x7FFFFFFF - member_offset)
+    throw std::runtime_error(std::string(op) + ": bad member range");
+}
+
+// launch_rollout with (dirs, mix, scale, J) next to the scalar sigma.
+static void launch_rollout_lowrank(uintptr_t theta, double sigma,
+                                   uintptr_t dirs, uintptr_t mix,
+                                   double scale, int J, uint32_t seed,
+                                   uint32_t iter, int horizon,
+                                   int member_offset, int pop_shard,
+                                   uintptr_t obs_mu, uintptr_t obs_nu,
+                                   uintptr_t env_A, uintptr_t env_B,
+                                   uintptr_t fitness,
+                                   uintptr_t obs_stat_part,
+                                   uintptr_t obs_stat, uintptr_t stream) {
+  if (pop_shard <= 0) return;
+  if (horizon < 1)
+    throw std::runtime_error("es_rollout_mlp_lowrank: horizon must be >= 1");
+  check_lowrank("es_rollout_mlp_lowrank", J, member_offset, pop_shard);
+  hipLaunchKernelGGL(es_rollout_mlp_lowrank, dim3(pop_shard), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)theta, (float)sigma,
+                     (const float*)dirs, (const float*)mix, (float)scale, J,
+                     seed, iter, horizon, member_offset,
+                     (const float*)obs_mu, (const float*)obs_nu,
+                     (const float*)env_A, (const float*)env_B,
+                     (float*)fitness, (float*)obs_stat_part,
+                     (float*)obs_stat);
+  check(hipGetLastError(), "es_rollout_mlp_lowrank launch");
+  hipLaunchKernelGGL(obs_stat_reduce, dim3(2 * OBS_HOST), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)obs_stat_part,
+                     pop_shard, (float*)obs_stat);
+  check(hipGetLastError(), "obs_stat_reduce launch");
+}
+
+// out is [n_members][NPARAMS]; one workgroup per member.
+static void launch_perturb_lowrank(uintptr_t theta, double sigma,
+                                   uintptr_t dirs, uintptr_t mix,
+                                   double scale, int J, uint32_t seed,
+                                   uint32_t iter, int member_offset,
+                                   int n_members, uintptr_t out,
+                                   uintptr_t stream) {
+  if (n_members <= 0) return;
+  check_lowrank("es_perturb_lowrank", J, member_offset, n_members);
+  hipLaunchKernelGGL(es_perturb_lowrank, dim3(n_members), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)theta, (float)sigma,
+                     (const float*)dirs, (const float*)mix, (float)scale, J,
+                     seed, iter, member_offset, (float*)out);
+  check(hipGetLastError(), "es_perturb_lowrank launch");
+}
+
 // ---- Deep GA launchers ------------------------------------------------------
 // ga_truncate counts over all n per thread and stops at 65536 members;
 // ga_survivors and ga_decode carry the row in grid.y.
@@ -1185,6 +1254,19 @@ PYBIND11_MODULE(_ops, m) {
         py::arg("wsum"), py::arg("pair_begin"), py::arg("pair_end"),
         py::arg("seed"), py::arg("iter"), py::arg("nparams"),
         py::arg("grad_part"), py::arg("grad"), py::arg("stream"));
+  m.attr("LOWRANK_DIRS_MAX") = LOWRANK_DIRS_MAX_HOST;
+  m.def("es_rollout_mlp_lowrank", &launch_rollout_lowrank, py::arg("theta"),
+        py::arg("sigma"), py::arg("dirs"), py::arg("mix"), py::arg("scale"),
+        py::arg("J"), py::arg("seed"), py::arg("iter"), py::arg("horizon"),
+        py::arg("member_offset"), py::arg("pop_shard"), py::arg("obs_mu"),
+        py::arg("obs_nu"), py::arg("env_A"), py::arg("env_B"),
+        py::arg("fitness"), py::arg("obs_stat_part"), py::arg("obs_stat"),
+        py::arg("stream"));
+  m.def("es_perturb_lowrank", &launch_perturb_lowrank, py::arg("theta"),
+        py::arg("sigma"), py::arg("dirs"), py::arg("mix"), py::arg("scale"),
+        py::arg("J"), py::arg("seed"), py::arg("iter"),
+        py::arg("member_offset"), py::arg("n_members"), py::arg("out"),
+        py::arg("stream"));
   m.attr("GA_TRUNCATE_MAX") = GA_TRUNCATE_MAX_HOST;
   m.attr("GA_ROWS_MAX") = GA_ROWS_MAX_HOST;
   m.def("ga_parents", &launch_ga_parents, py::arg("seed"), py::arg("gen"),

@@ -7,6 +7,7 @@ from .engine import (  # noqa: F401
 )
 from .cartpole import CartPoleESEngine  # noqa: F401
 from .ga import GAConfig, GAEngine  # noqa: F401
+from .lmmaes import LMMAESConfig, LMMAESEngine  # noqa: F401
 from .lstm import LSTMESEngine, init_theta_lstm  # noqa: F401
 from .lstm_cartpole import LSTMCartPoleESEngine  # noqa: F401
 from .map_elites import MapElitesConfig, MapElitesEngine  # noqa: F401

@@ -2209,5 +2209,122 @@ def es_rollout_lstm_cartpole(theta, sigma, seed, iteration, horizon,
     return out + final
 
 
+# ---------------------------------------------------------------------------
+# Low-rank correlated perturbations (lowrank_kernels.hip): members sampled
+# through T = scale * I + dirs^t mix dirs instead of the identity.  The
+# kernels know nothing of the algorithm that owns (dirs, mix, scale);
+# fiber_amd.es.lmmaes derives them for LM-MA-ES.
+# ---------------------------------------------------------------------------
+
+LOWRANK_DIRS_MAX = _OPS.LOWRANK_DIRS_MAX if _OPS else 32
+
+
+def _check_lowrank(theta, dirs, mix, scale):
+    """``dirs[J][NPARAMS]`` and ``mix[J][J]`` next to ``theta``; returns
+    ``(J, scale)``."""
+    for name, t in (("dirs", dirs), ("mix", mix)):
+        if not torch.is_tensor(t):
+            raise TypeError("%s must be a tensor, got %s"
+                            % (name, type(t).__name__))
+        _check(t, name)
+        if t.device != theta.device:
+            raise TypeError("%s is on %s, theta on %s"
+                            % (name, t.device, theta.device))
+    if dirs.dim() != 2 or dirs.shape[1] != NPARAMS:
+        raise ValueError("dirs must be [J, %d], got %s"
+                         % (NPARAMS, tuple(dirs.shape)))
+    J = dirs.shape[0]
+    if J > LOWRANK_DIRS_MAX:
+        raise ValueError("dirs holds %d directions, the kernels take %d"
+                         % (J, LOWRANK_DIRS_MAX))
+    if tuple(mix.shape) != (J, J):
+        raise ValueError("mix must be [%d, %d] for these dirs, got %s"
+                         % (J, J, tuple(mix.shape)))
+    if J and dirs.data_ptr() % 16:
+        raise ValueError("dirs must be 16-byte aligned")
+    scale = float(scale)
+    if not math.isfinite(scale):
+        raise ValueError("scale must be finite, got %r" % scale)
+    return J, scale
+
+
+def es_rollout_mlp_lowrank(theta, sigma, dirs, mix, scale, seed, iteration,
+                           horizon, member_offset, pop_shard, obs_mu, obs_nu,
+                           env_A, env_B):
+    """``es_rollout_mlp`` with correlated perturbations: member ``2k``
+    evaluates ``theta + sigma * d_k`` and member ``2k + 1`` evaluates
+    ``theta - sigma * d_k``, where ``d_k = scale * z_k + dirs^t (mix (dirs
+    z_k))`` and ``z_k`` is the draw ``es_rollout_mlp`` gives pair ``k``.
+    Returns ``(fitness[pop_shard], obs_stat[9])``; with ``J = 0`` and
+    ``scale = 1`` both are bit-identical to ``es_rollout_mlp``'s.
+
+    ``dirs`` is fp32 ``[J][NPARAMS]``, 16-byte aligned, ``0 <= J <=
+    LOWRANK_DIRS_MAX``; ``mix`` is fp32 ``[J][J]``, of which the lower
+    triangle (``mix[k][l]``, ``l <= k``) is read and the rest ignored;
+    ``scale`` a finite float.  For ``J = 0`` pass ``[0][NPARAMS]`` and
+    ``[0][0]``.  The values must be finite (not checked on the device).
+    Every sum in the kernel has a fixed order: two launches give the same
+    bits.
+
+    Everything is validated before the launch: TypeError for dtype, device
+    or contiguity, ValueError for shapes, ``J`` out of range, alignment, an
+    odd ``pop_shard`` or ``member_offset``, or ``horizon < 1``."""
+    ops = _require_ops()
+    if int(horizon) < 1:
+        raise ValueError("horizon must be >= 1, got %d" % int(horizon))
+    (pop_shard, member_offset, horizon, _, fitness, obs_stat,
+     part) = _rollout_prelude(theta, NPARAMS, False, "", pop_shard,
+                              member_offset, horizon, obs_mu, obs_nu, env_A,
+                              env_B)
+    J, scale = _check_lowrank(theta, dirs, mix, scale)
+    with torch.cuda.device(theta.device):
+        ops.es_rollout_mlp_lowrank(
+            theta.data_ptr(), float(sigma), dirs.data_ptr(), mix.data_ptr(),
+            scale, J, int(seed) & 0xFFFFFFFF, int(iteration) & 0xFFFFFFFF,
+            horizon, member_offset, pop_shard, obs_mu.data_ptr(),
+            obs_nu.data_ptr(), env_A.data_ptr(), env_B.data_ptr(),
+            fitness.data_ptr(), part.data_ptr(), obs_stat.data_ptr(),
+            _stream())
+    return fitness, obs_stat
+
+
+def es_perturb_lowrank(theta, sigma, dirs, mix, scale, seed, iteration,
+                       member_offset, n_members, out=None):
+    """The parameters ``es_rollout_mlp_lowrank`` rolls out for the members
+    ``member_offset .. member_offset + n_members - 1``, as fp32 rows
+    ``params[n_members][NPARAMS]`` (before the kernel rounds the weights to
+    bf16): the same device function with a global row as its sink, one
+    workgroup per member.  ``out`` (optional) receives them.
+
+    Arguments and errors as ``es_rollout_mlp_lowrank``; ``n_members >= 1``
+    may be odd, ``member_offset`` must be even."""
+    ops = _require_ops()
+    _check_policy_on((("theta", theta),), theta, NPARAMS, False)
+    n_members, member_offset = int(n_members), int(member_offset)
+    if n_members < 1 or member_offset < 0 or member_offset % 2 \
+            or member_offset + n_members >= 2 ** 31:
+        raise ValueError("n_members must be >= 1, member_offset even and "
+                         ">= 0 (antithetic pairs), got %d, %d"
+                         % (n_members, member_offset))
+    J, scale = _check_lowrank(theta, dirs, mix, scale)
+    if out is None:
+        out = torch.empty(n_members, NPARAMS, dtype=torch.float32,
+                          device=theta.device)
+    else:
+        _check(out, "out")
+        if out.device != theta.device:
+            raise TypeError("out is on %s, theta on %s"
+                            % (out.device, theta.device))
+        if tuple(out.shape) != (n_members, NPARAMS):
+            raise ValueError("out must be [%d, %d], got %s"
+                             % (n_members, NPARAMS, tuple(out.shape)))
+    with torch.cuda.device(theta.device):
+        ops.es_perturb_lowrank(
+            theta.data_ptr(), float(sigma), dirs.data_ptr(), mix.data_ptr(),
+            scale, J, int(seed) & 0xFFFFFFFF, int(iteration) & 0xFFFFFFFF,
+            member_offset, n_members, out.data_ptr(), _stream())
+    return out
+
+
 def ops_available():
     return _OPS is not None

@@ -49,6 +49,12 @@ class build_ext(_build_ext):
             # separable-NES rollout + two-row gradient: the same arrangement
             os.path.join(ROOT, "fiber_amd", "csrc", "ops",
                          "snes_kernels.hip"),
+            # low-rank correlated perturbations (LM-MA-ES): the policy fill
+            # with its two passes over the direction rows, in front of the
+            # shared step loop; the same arrangement, on this command 72
+            # VGPRs and no scratch (profiles/lmmaes.md)
+            os.path.join(ROOT, "fiber_amd", "csrc", "ops",
+                         "lowrank_kernels.hip"),
             # Deep GA rollout, truncation and seed-chain decode: the same
             # arrangement
             os.path.join(ROOT, "fiber_amd", "csrc", "ops",
